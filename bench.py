@@ -12,7 +12,14 @@ Units:
     between plies; every ply's action / reward / done stored to HBM).
 `--steps K --warmup W` run exactly W untimed and K timed bench steps.
 
-    python bench.py [--gpus N --steps K --warmup W]
+A plain run sets up, warms up, times the K steps and prints the result line.
+`--dump-outputs DIR` also writes the last timed step's outputs as
+DIR/<name>.npy (dump_outputs); the inputs are fixed by the arguments (seed 0),
+so two builds can be compared array for array.  `--full` adds everything
+beside the headline: the side measurements (`--no-side` drops them) and the
+CPU baselines (`--no-cpu-baseline` drops them).
+
+    python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
 With --gpus N > 1 and no WORLD_SIZE in the environment, bench.py starts the N
@@ -27,7 +34,7 @@ Rank 0 prints one JSON line.  `roofline` prices the dominant kernel
 (40W + 11 = 51 B at 8x8) x env-steps per launch over its average launch time
 (HIP events on the launch stream); `traffic` is the measured HBM bytes per
 launch from the rocprofv3 PMC summary committed under profiles/; the kernel's
-binding limit is integer VALU issue (`valu`).  `cpu_baseline` times the
+binding limit is integer VALU issue (`valu`).  With `--full`, `cpu_baseline` times the
 bitboard CPU engine (oracle/cpu_bitboard.cpp: the kernels' rules templates
 compiled for the host) and the scalar restatement of othello.py's ray walk
 (oracle/othello_oracle.c) on the host cores over bounded samples.
@@ -217,9 +224,13 @@ def parse_args(argv=None):
     ap.add_argument("--board-size", type=int, default=8)
     ap.add_argument("--policy", default="random", choices=["random", "greedy", "maximin1", "maximin2", "maximin3"])
     ap.add_argument("--no-record", action="store_true", help="do not store per-ply action/reward/done")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also run the side measurements and the CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs to DIR/<name>.npy (float32)")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-side", action="store_true", help="skip the side measurements")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-side", action="store_true", help="with --full: skip the side measurements")
     ap.add_argument("--dry-run", action="store_true",
                     help="ranks, process group and shard plan only (no GPU call); for CPU tests")
     return ap.parse_args(argv)
@@ -390,9 +401,11 @@ def main(argv=None):
     else:
         wall_max, wdl_total = wall, wdl
     wdl_total = [int(x) for x in wdl_total.cpu().tolist()]
+    if args.dump_outputs:  # before the side measurements, which reuse the output buffers
+        dump_outputs(args.dump_outputs, env, (acts, rews, dns), wdl, base, rank, world)
 
     side = {}
-    if not args.no_side and world == 1 and rank == 0:
+    if args.full and not args.no_side and world == 1 and rank == 0:
         side = side_measurements(env.env, args.policy, E, n, W, dev, stream, P=P, bufs=(acts, rews, dns),
                                  burst_us=kern_ms * 1e3 / args.steps)
 
@@ -400,7 +413,7 @@ def main(argv=None):
         out = make_record(args, world, G, E, P, n, record, wall_max, kern_ms, wdl_total, solo=solo,
                           shared_device=shared)
         out.update(side)
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(args.cpu_seconds, n)
         if side:
             out["side_summary"] = side_summary(side, out)  # last: a truncated tail still shows it
@@ -409,6 +422,39 @@ def main(argv=None):
     if world > 1:
         dist.destroy_process_group()
     return 0
+
+
+DUMP_BUDGET_BYTES = 60_000_000  # of array data over all ranks; the .npy headers are a few hundred bytes
+
+
+def dump_outputs(path, env, bufs, wdl, base, rank, world):
+    """--dump-outputs: what the last timed step handed its caller, as float32
+    DIR/<name>.npy (<name>_rank<r>.npy at N > 1): step_policy's per-ply
+    `actions`, `rewards` and `dones` (P, K), the boards it left behind (`board`:
+    the absolute colours, `possible_moves`: the legal plane, (K, N, N)), this
+    rank's W/D/L tally (`wdl`) and `env_ids` (K), the global ids of the boards
+    written.  K is every board of the shard, or the sorted sample of them that
+    RandomState(0) picks when all would exceed the size budget: the same boards
+    on every run with the same arguments."""
+    import numpy as np
+    import torch
+    E, n = env.num_envs, env.board_size
+    P = bufs[0].shape[0] if bufs[0] is not None else 0
+    per_board = 4 * (3 * P + 2 * n * n) + 8
+    K = min(E, DUMP_BUDGET_BYTES // world // per_board)
+    pick = np.arange(E) if K == E else np.sort(np.random.RandomState(0).choice(E, K, replace=False))
+    idx = torch.from_numpy(pick).to(env.device)
+    out = {"env_ids": torch.from_numpy(pick + base), "wdl": wdl.reshape(3)}
+    for name, t in zip(("actions", "rewards", "dones"), bufs):
+        if t is not None:
+            out[name] = t.index_select(1, idx)
+    out["board"] = env.observe("absolute", torch.float32).index_select(0, idx)
+    out["possible_moves"] = env.observe("legal", torch.float32).index_select(0, idx)
+    os.makedirs(path, exist_ok=True)
+    tag = "" if world == 1 else "_rank%d" % rank
+    for name, t in out.items():
+        wide = name in ("env_ids", "wdl")  # counts and ids beyond float32's 2^24: float64
+        np.save(os.path.join(path, name + tag + ".npy"), t.to(torch.float64 if wide else torch.float32).cpu().numpy())
 
 
 def make_record(args, world, G, E, P, n, record, wall_max, kern_ms, wdl_total, solo=None, shared_device=False,

@@ -30,6 +30,9 @@ def test_step_bytes_follow_survey_8d():
 def test_plan_defaults_per_config():
     a = bench.parse_args([])
     assert (a.steps, a.warmup) == (50, 10)
+    assert a.full is False and a.dump_outputs is None  # a plain run: the headline only
+    f = bench.parse_args(["--full", "--dump-outputs", "d", "--steps", "3"])
+    assert f.full is True and f.dump_outputs == "d" and f.steps == 3
     assert bench.plan(a, 1, 0) == (65536, 0, 65536, 100)  # config 2
     a8 = bench.parse_args(["--gpus", "8"])
     G, base, E, P = bench.plan(a8, 8, 7)
