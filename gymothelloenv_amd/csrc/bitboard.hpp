@@ -14,10 +14,6 @@
 #include <stdint.h>
 #include <type_traits>
 
-#ifndef OTH_OPENING_PHILOX
-#define OTH_OPENING_PHILOX 0  // opening-length draws by Philox (round-5 spec; A/B timing arm, round 6)
-#endif
-
 #if defined(__HIPCC__)
 #define OTH_HD __host__ __device__ __forceinline__
 #else
@@ -1280,15 +1276,11 @@ OTH_HD uint32_t fmix32(uint32_t h) {
     return h;
 }
 OTH_HD uint32_t opening_draw(uint64_t seed, uint32_t id, uint64_t ply, uint32_t purpose) {
-#if OTH_OPENING_PHILOX  // A/B timing arm only (other values: the oracle follows the hash)
-    return philox_x(seed, id, ply, purpose);
-#else
     // the key depends on the seed and the purpose alone (loop-invariant: hoisted out
     // of the play loops), the ply enters once, the env id last
     const uint32_t key = fmix32((uint32_t)seed ^ fmix32((uint32_t)(seed >> 32) ^ purpose * 0x7FEB352Du));
     const uint32_t c = fmix32(key ^ (uint32_t)ply ^ (uint32_t)(ply >> 32) * 0x9E3779B9u);
     return fmix32(c ^ id);
-#endif
 }
 OTH_HD uint32_t pick4(const U4& u, uint32_t j) {
 #if defined(__HIP_DEVICE_COMPILE__)

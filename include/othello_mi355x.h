@@ -108,8 +108,22 @@ enum {
 
 /* OthelloBaseEnv.__init__ (othello.py:222-254) for n_envs boards of size
  * board_size (clamped to >= 4 like othello.py:230; > 16 is OTH_EINVAL).
- * seed / env_id_base key the Philox RNG of the on-device policies: env i uses
- * id env_id_base + i, so a sharded run reproduces an unsharded one.
+ * seed / env_id_base key every random draw: env i uses id env_id_base + i
+ * (mod 2^32), so a sharded run reproduces an unsharded one.  Two stateless
+ * functions of (seed, id, 64-bit counter, purpose) draw everything:
+ *   - moves and samples: Philox4x32-10 with key (seed lo, seed hi) and counter
+ *     (id, counter lo, counter hi, purpose).  Purpose 0: the random move of
+ *     ply g is word g % 4 of the block with counter g / 4.  Purpose 3: the
+ *     sampler's uniform is (word 0 of the block with the sample counter) >> 8,
+ *     times 2^-24.
+ *   - random-opening lengths: three murmur3 32-bit finalisers (fmix32),
+ *       key = fmix32(seed lo ^ fmix32(seed hi ^ purpose * 0x7FEB352D)),
+ *       word = fmix32(fmix32(key ^ ply lo ^ ply hi * 0x9E3779B9) ^ id),
+ *     with purpose 1 at an auto-reset (the counter is the terminal ply; the
+ *     call counter in oth_step_vs) and purpose 2 in oth_reset / oth_reset_vs.
+ * A 32-bit word u picks index floor(u * n / 2^32) among n choices: the legal
+ * moves in ascending order, or the initial_rand_steps / 2 + 1 opening lengths
+ * 0, 2, ..
  * initial_rand_steps: SimpleOthelloEnv's random-opening length bound
  * (othello.py:62-63) applied by oth_reset and auto-reset.  Boards start reset. */
 int oth_create(int32_t n_envs, int32_t board_size, uint32_t flags, uint64_t seed, uint32_t env_id_base,
@@ -196,7 +210,7 @@ int oth_greedy_actions(oth_env *env, int32_t *out, oth_stream_t stream);
  * anything is launched. */
 int oth_policy_actions(oth_env *env, int32_t policy, int32_t *out, oth_stream_t stream);
 
-/* Observations: layout OTH_OBS_*, dtype OTH_I8..OTH_F64, out (E, planes, N, N). */
+/* Observations: layout OTH_OBS_*, dtype OTH_I8..OTH_BF16, out (E, planes, N, N). */
 int oth_observe(oth_env *env, int32_t layout, int32_t dtype, void *out, oth_stream_t stream);
 
 /* Copy the state out / in (exchange format above).  In oth_set_state any of

@@ -1,5 +1,6 @@
 // Host build of csrc/bitboard.hpp (the same templates the kernels use) for CPU
-// tests: legal_moves<N> / flips<N> / select_bit / philox4 and the one-word
+// tests: legal_moves<N> / flips<N> / select_bit / philox4 and the draws
+// (action_draw, opening_draw, scale_index) and the one-word
 // fills scan + bit-plane greedy (OneWord<N>) exported with C linkage.
 // Built by tests/test_bitboard_host.py with g++; test infrastructure only.
 #include <stdint.h>
@@ -180,5 +181,16 @@ void host_philox4(uint64_t seed, uint32_t id, uint64_t ctr, uint32_t purpose, ui
     out[1] = u.y;
     out[2] = u.z;
     out[3] = u.w;
+}
+// the three draws the kernels call, one tuple per element (every field at full width)
+void host_opening_draw(int n, const uint64_t* seed, const uint32_t* id, const uint64_t* ply, const uint32_t* purpose,
+                       uint32_t* out) {
+    for (int i = 0; i < n; ++i) out[i] = opening_draw(seed[i], id[i], ply[i], purpose[i]);
+}
+void host_action_draw(int n, const uint64_t* seed, const uint32_t* id, const uint64_t* g, uint32_t* out) {
+    for (int i = 0; i < n; ++i) out[i] = action_draw(seed[i], id[i], g[i]);
+}
+void host_scale_index(int n, const uint32_t* u, const int32_t* m, int32_t* out) {
+    for (int i = 0; i < n; ++i) out[i] = scale_index(u[i], m[i]);
 }
 }

@@ -34,6 +34,13 @@ def hostlib():
     L.host_fills_flips.argtypes = [ctypes.c_int, ctypes.c_int, P, P, P, P]
     L.host_greedy_planes_w.argtypes = [ctypes.c_int, ctypes.c_int, P, P, P, P]
     L.host_philox4.argtypes = [ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint32, P]
+    L.host_philox4.restype = None
+    L.host_opening_draw.argtypes = [ctypes.c_int, P, P, P, P, P]
+    L.host_opening_draw.restype = None
+    L.host_action_draw.argtypes = [ctypes.c_int, P, P, P, P]
+    L.host_action_draw.restype = None
+    L.host_scale_index.argtypes = [ctypes.c_int, P, P, P]
+    L.host_scale_index.restype = None
     return L
 
 
