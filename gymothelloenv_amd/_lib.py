@@ -35,6 +35,8 @@ OTH_OBS_LEGAL = 4
 OTH_I8, OTH_I32, OTH_I64, OTH_F32, OTH_F64, OTH_BF16 = range(6)
 OTH_MASKED_SAMPLE, OTH_MASKED_MODE, OTH_MASKED_EVAL = range(3)
 OTH_MASKED_FULL_ENTROPY = 4
+OTH_PLAYOUT_ROOT, OTH_PLAYOUT_MOVES = 0, 1  # oth_playouts modes
+OTH_PLAYOUTS_MAX = 65536
 OTH_GRAPH_SLOTS = 64
 OTH_GRAPH_COUNTER_SHIFT = 40
 
@@ -73,6 +75,7 @@ SIGNATURES = {
     "oth_step_observe": (_I32, [_P, _P, _P, _P, _I32, _I32, _P, _P]),
     "oth_step_sync": (_I32, [_P, _I32, _I32, _I32, _I32, ctypes.POINTER(_P), _P]),
     "oth_step_policy": (_I32, [_P, _I32, _I32, _P, _P, _P, _P]),
+    "oth_playouts": (_I32, [_P, _I32, _I32, _U64, _U32, _U64, _P, _P, _P, _P]),
     "oth_reset_vs": (_I32, [_P, _I32, _P, _P, _P]),
     "oth_step_vs": (_I32, [_P, _I32, _P, _P, _P, _P, _P, _P]),
     "oth_step_vs_observe": (_I32, [_P, _I32, _P, _P, _P, _P, _P, _I32, _I32, _P, _P]),

@@ -3,7 +3,8 @@ travels with the repo snapshot to the GPU box).
 
 The kernels are templates over the board size N; csrc/kernels_n.hip is
 compiled once per N (-DOTH_N=4..16) in parallel, csrc/play_rand_n.hip (the
-fused random-play kernels, its own scheduler flags) once per N = 4..11, csrc/capi.hip holds
+fused random-play kernels, its own scheduler flags) once per N = 4..11, csrc/playouts_n.hip
+(oth_playouts) once per N, csrc/capi.hip holds
 the C ABI, and the objects are linked into one shared library.
 
 Reproducibility: objects go to a fixed directory (`_objs/`, git-ignored) so the
@@ -25,11 +26,16 @@ ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 SIZES = list(range(4, 17))
 SOURCES = ("capi.hip", "kernels_n.hip", "play_rand_n.hip", "masked.hip", "device.hpp", "launch.hpp", "bitboard.hpp",
-           "masked.hpp", "ply.hpp", "sample_step.hpp", "maximin_wave.hpp")
+           "masked.hpp", "ply.hpp", "sample_step.hpp", "maximin_wave.hpp", "playouts_n.hip", "playouts.hpp")
 PLAY_SIZES = list(range(4, 12))  # k_play_rand (one-word boards) and k_play_rand_w (two-word boards)
 # play_rand_n.hip: the max-ILP machine scheduler (one wave per SIMD: latency hidden by the schedule
 # counts, occupancy does not); the rest of the library keeps the default scheduler
 PLAY_FLAGS = ["-mllvm", "-amdgpu-sched-strategy=max-ilp"]
+# playouts_n.hip (oth_playouts), every board size: a unit of its own so that it can carry scheduler flags
+# of its own.  Several waves per SIMD share its latency, and max-ilp measured within the spread of two
+# runs at 65,536 boards x 8, -1.5 % at 1,024 boards x 64 per move and -4 % on one board x 65,536
+# (profiles/playouts_sched_ab.json): it keeps the default scheduler
+PLAYOUT_FLAGS = []
 DEPS = [os.path.join(CSRC, f) for f in SOURCES] + [os.path.join(ROOT, "include", "othello_mi355x.h")]
 OUT = os.path.join(HERE, "liboth_mi355x.so")
 OBJDIR = os.path.join(HERE, "_objs")
@@ -55,7 +61,7 @@ def source_hash(extra_flags=(), out=OUT):
         with open(p, "rb") as f:
             h.update(f.read())
         h.update(b"\0")
-    h.update(" ".join([ARCH] + BASE_FLAGS + play_flags(out) + list(extra_flags)).encode())
+    h.update(" ".join([ARCH] + BASE_FLAGS + play_flags(out) + PLAYOUT_FLAGS + list(extra_flags)).encode())
     return h.hexdigest()
 
 
@@ -97,6 +103,8 @@ def build(force=False, verbose=True, extra_flags=(), out=OUT, jobs=None, only_si
               for n in SIZES]
     units += [(os.path.join(CSRC, "play_rand_n.hip"), os.path.join(objdir, "play_rand_n%d.o" % n),
                ["-DOTH_N=%d" % n] + play_flags(out)) for n in PLAY_SIZES]
+    units += [(os.path.join(CSRC, "playouts_n.hip"), os.path.join(objdir, "playouts_n%d.o" % n),
+               ["-DOTH_N=%d" % n] + PLAYOUT_FLAGS) for n in SIZES]
 
     def compile_one(u):
         src, obj, defs = u
@@ -111,7 +119,8 @@ def build(force=False, verbose=True, extra_flags=(), out=OUT, jobs=None, only_si
     reuse = []
     if only_sizes is not None:
         keep = {"capi.o", "masked.o"} | {"kernels_n%d.o" % n for n in only_sizes} | {"play_rand_n%d.o" % n
-                                                                                   for n in only_sizes}
+                                                                                   for n in only_sizes} | {
+            "playouts_n%d.o" % n for n in only_sizes}
         reuse = [os.path.join(OBJDIR, os.path.basename(u[1])) for u in units if os.path.basename(u[1]) not in keep]
         units = [u for u in units if os.path.basename(u[1]) in keep]
         missing = [o for o in reuse if not os.path.exists(o)]

@@ -388,6 +388,26 @@ int oth_step_policy(oth_env* env, int32_t policy, int32_t n_plies, int32_t* acti
     });
 }
 
+int oth_playouts(oth_env* env, int32_t mode, int32_t n_playouts, uint64_t seed, uint32_t id_key, uint64_t counter,
+                 int32_t* wdl, int32_t* score, int32_t* best, oth_stream_t stream) {
+    // the argument checks come before the device is touched
+    if (!env) return fail(OTH_EINVAL, "NULL oth_env");
+    if (!wdl) return fail(OTH_EINVAL, "wdl is NULL");
+    if (mode != OTH_PLAYOUT_ROOT && mode != OTH_PLAYOUT_MOVES) return fail(OTH_EINVAL, "unknown playout mode");
+    if (n_playouts < 1 || n_playouts > OTH_PLAYOUTS_MAX)
+        return fail(OTH_EINVAL, "n_playouts must be in [1, 65536]");
+    if (best && mode == OTH_PLAYOUT_ROOT) return fail(OTH_EINVAL, "best is per move: NULL in OTH_PLAYOUT_ROOT mode");
+    if (counter >> 56) return fail(OTH_EINVAL, "counter must be below 2^56");
+    const int64_t per_env = (int64_t)n_playouts * (mode == OTH_PLAYOUT_MOVES ? env->n * env->n : 1);
+    if ((int64_t)env->E * per_env > 0x7fffffffll)
+        return fail(OTH_EINVAL, "more than 2^31 - 1 playouts in one call: split the boards or the playouts");
+    if (int rc = use_device(env)) return rc;
+    return with_n(env->n, [&](auto NC) {
+        return launch_playouts<decltype(NC)::value>(env, mode, n_playouts, seed, id_key, counter, wdl, score, best,
+                                                    (hipStream_t)stream);
+    });
+}
+
 int oth_reset_vs(oth_env* env, int32_t opponent_policy, const int8_t* protagonist, const uint8_t* mask,
                  oth_stream_t stream) {
     OTH_CHECK_ENV(env);

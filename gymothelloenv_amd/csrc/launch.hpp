@@ -112,4 +112,9 @@ template <int N, int POL>
 void launch_play_rand(oth_env* env, int n_plies, int32_t* actions, int32_t* rewards, uint8_t* dones, uint64_t ply0,
                       hipStream_t st);
 
+// k_playouts (oth_playouts) in playouts_n.hip, every N, a unit of its own per board size
+template <int N>
+int launch_playouts(oth_env* env, int mode, int n_playouts, uint64_t seed, uint32_t id_key, uint64_t counter,
+                    int32_t* wdl, int32_t* score, int32_t* best, hipStream_t st);
+
 }  // namespace oth_host

@@ -118,4 +118,38 @@ class MaxiMinPolicy(object):
         return self.get_action(obs)
 
 
-__all__ = ['RandomPolicy', 'GreedyPolicy', 'MaxiMinPolicy', 'PROTAGONIST_TURN', 'OPPONENT_TURN', 'WHITE_DISK']
+class MonteCarloPolicy(object):
+    """Flat Monte-Carlo move selection (no reference counterpart: the rung after
+    MaxiMinPolicy): the possible move whose n_playouts random games, played on
+    the device (oth_playouts, per move), end best for the side to move -- the
+    largest wins - losses, lowest square on ties.  Playouts are keyed by `seed`
+    and a call counter that moves on with every move, so a seeded policy
+    replays its games move for move."""
+
+    def __init__(self, n_playouts=64, seed=0):
+        self.env = None
+        self.n_playouts = int(n_playouts)
+        self._seed = int(seed)
+        self.counter = 0
+
+    def reset(self, env):
+        self.env = _base(env)
+
+    def seed(self, seed):
+        self._seed = int(seed)
+        self.counter = 0
+
+    def get_action(self, obs):
+        vec = self.env._vec
+        self.env._sync()
+        a = int(vec.playout_actions(self.n_playouts, seed=self._seed, counter=self.counter).cpu()[0])
+        self.counter += 1
+        if a < 0:
+            raise ValueError('no possible moves')
+        return a
+
+    def get_test_action(self, obs):
+        return self.get_action(obs)
+
+
+__all__ = ['RandomPolicy', 'GreedyPolicy', 'MaxiMinPolicy', 'MonteCarloPolicy', 'PROTAGONIST_TURN', 'OPPONENT_TURN', 'WHITE_DISK']

@@ -27,6 +27,10 @@ _POLICIES.update({"maximin%d" % d: L.OTH_POLICY_MAXIMIN(d) for d in range(1, L.O
 
 BLACK_DISK, NO_DISK, WHITE_DISK = -1, 0, 1  # othello.py:10-12
 
+# playouts(seed=None) keys its draws with the env's seed XOR this constant (the 64-bit golden ratio),
+# so playouts never share a Philox key with the env's own play
+PLAYOUT_SEED_XOR = 0x9E3779B97F4A7C15
+
 
 _RAW_STREAM = getattr(torch._C, "_cuda_getCurrentRawStream", None)
 
@@ -85,6 +89,7 @@ class VecOthelloEnv(object):
         self._okbufs = None  # (rewards, dones) tensors step() has checked
         self._okobs = None  # (obs tensor, layout) step() / sample_step() have checked
         self._sample_calls = 0  # Philox counter of sample_actions
+        self._playout_calls = 0  # `counter` of the next playouts() call that gives none
         self._region_resets = None  # resets inside an open graph region (None: no region)
 
     # ------------------------------------------------------------------ utils
@@ -405,6 +410,61 @@ class VecOthelloEnv(object):
         L.check(self._lib.oth_counts_vs(self._h, _ptr(out), int(bool(reset)), self._stream()), "oth_counts_vs")
         return out
 
+    # ------------------------------------------------------ Monte-Carlo playouts
+    def playouts(self, n_playouts, per_move=False, seed=None, id_key=0, counter=None, score=False, best=False):
+        """n_playouts random games to the end from every board's position
+        (per_move=False: oth_playouts OTH_PLAYOUT_ROOT) or from the position after
+        each of its possible moves (per_move=True: OTH_PLAYOUT_MOVES), on private
+        copies: the boards, the ply counter and the tallies are left untouched.
+
+        Returns wdl, then score and best when asked: int32 tensors on this device,
+          wdl   (E, 3) or (E, N*N, 3): {wins, draws, losses} from the side to move
+                at the root; zeros for squares that are not possible moves and for
+                terminated boards;
+          score (E,) or (E, N*N): the summed final disc difference (root mover's
+                minus opponent's);
+          best  (E,), per_move only: the possible move of the largest wins - losses
+                (lowest square on ties), -1 without one.
+        seed=None: the env's seed XOR PLAYOUT_SEED_XOR, so the draws never share a
+        Philox key with the env's own play.  counter=None: `playout_counter`,
+        which then moves on by one; the same (seed, id_key, counter) repeats the
+        same playouts (include/othello_mi355x.h gives the draw of every ply)."""
+        R = int(n_playouts)
+        nn = self.board_size * self.board_size
+        if best and not per_move:
+            raise ValueError("best is the best possible move: it needs per_move=True")
+        key = (self.seed ^ PLAYOUT_SEED_XOR if seed is None else int(seed)) & (2 ** 64 - 1)
+        own = counter is None
+        ctr = self._playout_calls if own else int(counter)
+        shape = (self.num_envs, nn) if per_move else (self.num_envs,)
+        wdl = self._i32(*(shape + (3,)))
+        sc = self._i32(*shape) if score else None
+        bt = self._i32(self.num_envs) if best else None
+        L.check(self._lib.oth_playouts(self._h, L.OTH_PLAYOUT_MOVES if per_move else L.OTH_PLAYOUT_ROOT, R, key,
+                                       int(id_key) & 0xffffffff, ctr, _ptr(wdl), _ptr(sc), _ptr(bt), self._stream()),
+                "oth_playouts")
+        if own:
+            self._playout_calls += 1
+        res = (wdl,) + ((sc,) if score else ()) + ((bt,) if best else ())
+        return res[0] if len(res) == 1 else res
+
+    def playout_actions(self, n_playouts, **kw):
+        """Flat Monte-Carlo move selection: every board's possible move with the
+        largest wins - losses over n_playouts random games each (playouts(per_move=True,
+        best=True)); int32 (E,), -1 for a board without a possible move."""
+        kw.pop("per_move", None)
+        kw.pop("best", None)
+        return self.playouts(n_playouts, per_move=True, best=True, **kw)[-1]
+
+    @property
+    def playout_counter(self):
+        """`counter` of the next playouts() call that does not give one."""
+        return self._playout_calls
+
+    @playout_counter.setter
+    def playout_counter(self, v):
+        self._playout_calls = int(v)
+
     def _sampler_inputs(self, logits, uniforms):
         """(logits rows, uniforms) checked before a launch reads them: the rows on
         this handle's device, one per board; uniforms float32 on it, >= E of them."""
@@ -560,7 +620,8 @@ class VecOthelloEnv(object):
         _no_capture("state_dict")
         b, m, lg = self.get_state()
         return {"boards": b, "meta": m, "legal": lg, "ply_counter": self.ply_counter,
-                "sample_calls": self._sample_calls, "board_size": self.board_size,
+                "sample_calls": self._sample_calls, "playout_calls": self._playout_calls,
+                "board_size": self.board_size,
                 "num_envs": self.num_envs}
 
     def load_state_dict(self, sd):
@@ -572,6 +633,7 @@ class VecOthelloEnv(object):
         self.set_state(sd["boards"], sd["meta"], sd["legal"])
         self.ply_counter = sd["ply_counter"]
         self._sample_calls = int(sd.get("sample_calls", 0))
+        self._playout_calls = int(sd.get("playout_calls", 0))
 
     # decoded views of the meta word
     def player_turn(self):

@@ -161,6 +161,60 @@ int oth_step_observe(oth_env *env, const int32_t *actions, int32_t *rewards, uin
 int oth_step_policy(oth_env *env, int32_t policy, int32_t n_plies, int32_t *actions, int32_t *rewards,
                     uint8_t *dones, oth_stream_t stream);
 
+/* Monte-Carlo playouts from the handle's live positions (no reference
+ * counterpart: the leaf evaluation of MCTS, flat Monte-Carlo move selection, a
+ * cheap value target).  From each board (OTH_PLAYOUT_ROOT), or from each board
+ * after each of its possible moves (OTH_PLAYOUT_MOVES), n_playouts = R games of
+ * uniformly random legal moves are played to the end on private copies.
+ *
+ * Handle state.  The call reads boards, meta and possible_moves and writes
+ * nothing of the handle: boards, meta, possible_moves, the ply counter, the
+ * graph offsets and both tallies (oth_counts, oth_counts_vs) stay as they are.
+ * It only enqueues work.  The handle's flags (sudden death, disk reward,
+ * auto-reset) and random-opening plies left in meta play no part.
+ *
+ * ROOT: for each env e and r in [0, R), a copy of env e's position plays random
+ *   moves until it is terminated.
+ * MOVES: for each env e, each square a set in the handle's stored
+ *   possible_moves[e] (not a recomputation: after oth_set_state with a narrower
+ *   mask only those squares are evaluated) and each r, the copy first takes
+ *   exactly oth_step's ply with action a (flags 0, no reset), then plays
+ *   randomly to the end.
+ *
+ * Draws.  Playout ply p (p = 0 is the first RANDOM ply, after the forced move
+ * of MOVES mode) draws like every random move: Philox4x32-10, purpose 0, key =
+ * this call's `seed` (not the handle's), counter g = counter * 256 + p (block
+ * g / 4, word g % 4); a playout has at most N*N - 4 < 256 random plies, and
+ * counter >= 2^56 is OTH_EINVAL.  The id is
+ *     id_key + (env_id_base + e) * S + a * R + r   (mod 2^32),
+ * S = R and a = 0 in ROOT mode, S = N*N*R in MOVES mode: a function of the
+ * global env id, the square and r alone, never of how playouts are mapped to
+ * lanes or of how many moves are legal, so a sharded run equals the unsharded
+ * one.
+ *
+ * Outputs (device pointers; every element is written, nothing needs zeroing):
+ *   wdl    required.  ROOT int32[E][3], MOVES int32[E][N*N][3]: {wins, draws,
+ *          losses} of the R playouts, counted from the side to move at the ROOT
+ *          of env e.  Squares not in possible_moves and boards already
+ *          terminated get zeros.
+ *   score  may be NULL.  ROOT int32[E], MOVES int32[E][N*N]: the sum over the R
+ *          playouts of (root mover's discs - opponent's discs) on the final board.
+ *   best   may be NULL; MOVES only (non-NULL in ROOT mode is OTH_EINVAL).
+ *          int32[E]: the possible move with the largest wins - losses, the
+ *          lowest square on ties; -1 for a terminated board or an empty
+ *          possible_moves.  Computed on the device in integers.
+ * OTH_EINVAL: NULL handle, NULL wdl, unknown mode, R < 1 or R > OTH_PLAYOUTS_MAX,
+ * more than 2^31 - 1 playouts in the call (E*R in ROOT mode, E*N*N*R in MOVES
+ * mode).  Every board size works.
+ *
+ * Under a HIP-graph capture the call is capturable (it only enqueues), but it
+ * bakes `counter` in: every replay repeats the same playouts.  It does not use
+ * the graph regions' counter offsets (oth_graph_begin). */
+enum { OTH_PLAYOUT_ROOT = 0, OTH_PLAYOUT_MOVES = 1 };
+#define OTH_PLAYOUTS_MAX 65536
+int oth_playouts(oth_env *env, int32_t mode, int32_t n_playouts /* R */, uint64_t seed, uint32_t id_key,
+                 uint64_t counter, int32_t *wdl, int32_t *score, int32_t *best, oth_stream_t stream);
+
 /* OthelloEnv (othello.py:96-214) for every env: the protagonist's colour per
  * env (protagonist: device int8[E] of +1 white / -1 black, NULL = all white,
  * the reference default) and an embedded opponent played on the device
