@@ -959,6 +959,52 @@ struct OneWord {
     // a row, reversed), an involution on the board's NN bits.
     static OTH_HD uint64_t turn180(uint64_t x) { return rev64(x) >> (64 - N * N); }
 
+    // The ray of step S from square 0 as a plain constant: bits S, 2S, ... below 64,
+    // no edge masks.  Shifted to a square it runs on across the row's end (and, on
+    // boards of N < 8, past the last square); flip_fills says why that is harmless.
+    static constexpr uint64_t ray0(int S) {
+        uint64_t x = 0;
+        for (int k = S; k < 64; k += S) x |= 1ull << k;
+        return x;
+    }
+    static constexpr uint64_t RAY_E = ray0(1), RAY_S = ray0(N), RAY_SE = ray0(N + 1), RAY_SW = ray0(N - 1);
+
+    // update_board's flips (othello.py:391-410) of a move on square a from the
+    // eight fills of the side to move (legal()'s t; t[d] = the opponent discs
+    // from which an own disc is reached going along d, so every square of t[d]
+    // is already capped and the run to flip along d is the contiguous part of
+    // ray d from a inside t[d]).  No ray table: the ray toward higher squares is
+    // ray0(S) << a, and the run is ray & t & (y - 1) with y = ray & ~t -- y's
+    // lowest bit is the first ray square outside the fill, y - 1 every bit below
+    // it.  The unmasked ray is exact here because of what a fill can hold:
+    //   * E, SE, SW: the scan propagates through O & INNER only, so t[d] holds
+    //     no edge-column square, and a ray can leave its row only by first
+    //     passing one (or starts on one, and then its first square is on the
+    //     other edge column): y's lowest bit lies at or before the wrap;
+    //   * S: the ray runs off the word; bits at or above N*N are in no fill.
+    // Toward lower squares the same on the board turned by 180 degrees
+    // (turn180), where direction d is direction d - 4 from square N*N - 1 - a;
+    // the four turned runs are turned back once.
+    // (The E and W runs by a carry instead -- t & ~(t + 2m), m the move's bit, one
+    // v_lshl_add_u64 and an and-not: 6 VALU fewer per ply, and slower on the
+    // MI355X: 66.8 against 65.1 us per 100-ply launch of 65,536 boards; DESIGN.md
+    // section 5.)
+    // a: any value; the shift counts are taken & 63, so they stay defined for
+    // an invalid action (negative, or >= N*N), whose flips the caller masks.
+    static OTH_HD uint64_t flip_fills(const uint64_t t[8], int a) {
+        constexpr uint64_t RAY[4] = {RAY_E, RAY_S, RAY_SE, RAY_SW};
+        const uint32_t su = (uint32_t)a & 63u, sd = (uint32_t)(N * N - 1 - a) & 63u;
+        uint64_t f = 0, g = 0;
+#pragma unroll
+        for (int d = 0; d < 4; ++d) {
+            const uint64_t tt = turn180(t[d + 4]);
+            const uint64_t ru = RAY[d] << su, rd = RAY[d] << sd;
+            f |= and3_64(ru, t[d], (ru & ~t[d]) - 1ull);
+            g |= and3_64(rd, tt, (rd & ~tt) - 1ull);
+        }
+        return f | turn180(g);
+    }
+
     // The horizontal axis by carries: stepping +1 from an own
     // disc through a run of opponent discs of the inner columns is a carry
     // chain of (P << 1) + pin, which clears the run and sets the square past

@@ -176,7 +176,8 @@ __device__ __forceinline__ void store_lane(const Lane<N>& s, uint64_t* __restric
 // ---------------------------------------------------------------------------
 // Engines: who computes legal moves and flips for a lane.
 //   Solo<N>: one lane per board, all 8 directions (any N).
-//   Fills<N> / FillsW<N>: flips from LDS ray tables and the legal scan's fills.
+//   Fills<N> / FillsW<N>: flips from the legal scan's fills and rays -- shifted
+//            constants on one-word boards, an LDS ray table on multi-word ones.
 //   Quartet<N>: four lanes per board (N <= 8): each lane of the quad scans
 //            one axis and the parts are or-ed through DPP quad_perm steps.
 // ---------------------------------------------------------------------------
@@ -184,6 +185,7 @@ template <int N>
 struct Solo {
     static constexpr int LANES = 1;
     static constexpr int RAY_WORDS = 0;
+    static constexpr bool FLIP_ANY = false;  // flip() is for a square of the board
     __device__ __forceinline__ Solo(int, const uint64_t*) {}
     __device__ __forceinline__ BB<Geo<N>::W> legal(const BB<Geo<N>::W>& P, const BB<Geo<N>::W>& O) const {
         if constexpr (Geo<N>::W == 1) {  // the dword-pair scan (fills unused, so dead)
@@ -209,7 +211,7 @@ struct Solo {
 
 // TURNED: the tables of the directions toward lower squares (d >= 4) hold
 // their rays on the board turned by 180 degrees (square s -> N*N-1-s), still
-// indexed by the unturned square (Fills).
+// indexed by the unturned square (the handle's table, k_fill_rays).
 template <int N, bool TURNED = false, bool SYNC = true>
 __device__ __forceinline__ void fill_rays(uint64_t* rays) {
     for (int i = threadIdx.x; i < 8 * 64; i += BLOCK) {
@@ -267,7 +269,8 @@ struct RayMath {
     }
 };
 
-// Fills<N>: flips from the ray tables and the legal scan's fills.  legal_moves' axis scans
+// Fills<N>: flips from the legal scan's fills and shifted ray constants (no
+// table, no LDS).  legal_moves' axis scans
 // compute, for the side to move, the fills t(dir) = opponent discs reachable
 // from an own disc through contiguous opponent discs stepping in direction dir
 // (the scan shifts them once more onto the empty squares).  Kept in registers
@@ -283,14 +286,14 @@ template <int N>
 struct Fills {
     static_assert(Geo<N>::W == 1, "fills engine is for one-word boards (N <= 8)");
     static constexpr int LANES = 1;
-    static constexpr int RAY_WORDS = 8 * 64;
+    static constexpr int RAY_WORDS = 0;     // no table in LDS
+    static constexpr bool FLIP_ANY = true;  // flip() is defined for every a (its shift counts are masked)
     static constexpr int STEPS = Pro<N, 0, 1>::STEPS;
     static constexpr uint64_t BD = Geo<N>::BOARD.w[0], IN = Geo<N>::INNER.w[0];
-    const uint64_t* rays;
     // t[d] = the fill to use for ray direction d (rays: E, S, SE, SW, W, N, NW, NE):
     // up directions (+S) use the -S fill, down directions the +S fill
     mutable uint64_t t[8];
-    __device__ __forceinline__ Fills(int, const uint64_t* lds) : rays(lds) {}
+    __device__ __forceinline__ Fills(int, const uint64_t*) {}
 
     // get_possible_actions for mover P, keeping the fills: the axis-paired scan
     // on dwords (bitboard.hpp OneWord: v_bitop3 / v_and_or, carry-chain horizontal axis)
@@ -299,48 +302,19 @@ struct Fills {
         r.w[0] = OneWord<N>::legal(Pb.w[0], Ob.w[0], t);
         return r;
     }
-    // FIRST: the eight ray loads issued together before the runs (a scheduling
-    // barrier after them), one LDS round trip instead of the two the backend's
-    // interleaving left: greedy 100-ply launches 1.296 -> 1.264 us per ply, 6x6
-    // random 0.791 -> 0.775, but 8x8 random 0.685 -> 0.689 (profiles/r06/t, u),
-    // so k_play_rand asks for it except at 8x8 random play
-    template <bool FIRST = false>
+    // update_board's flips for a move on square a (OneWord::flip_fills: the rays
+    // are four constants, held in SGPRs, shifted to a and to the turned square).
+    // Before, the eight rays were read from a 4-KiB LDS table at rays + a, a
+    // round trip that could start only once the pick's sel8 read had produced a,
+    // with nothing independent left to cover it: 8x8 random play 67.9 -> 65.1 us
+    // per 100-ply launch of 65,536 boards for +8 VALU per ply (DESIGN.md section
+    // 5).  (RayMath's rays with their column masks, +38 VALU per ply, had lost
+    // to that table: 0.671 -> 0.696 us per ply, profiles/r04/fm/ab.jsonl; a fill
+    // holds no edge-column square off the vertical axis, so the masks are not
+    // needed.)
     __device__ __forceinline__ BB<1> flip(const BB<1>&, const BB<1>&, int a) const {
-        const uint64_t* r = rays + a;
-        // (the rays computed by RayMath instead of read from the LDS table: 8x8
-        // 0.671 -> 0.696 us per ply, greedy +2.8 %, 6x6 +3.3 %: +38 VALU per ply cost
-        // more than the LDS round trip they remove; profiles/r04/fm/ab.jsonl)
-        uint64_t rr[8];
-        if constexpr (FIRST) {
-#pragma unroll
-            for (int d = 0; d < 8; ++d) rr[d] = r[64 * d];
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        auto ray_of = [&](int d) __attribute__((always_inline)) { return FIRST ? rr[d] : r[64 * d]; };
-        uint64_t f = 0;
-#pragma unroll
-        for (int d = 0; d < 4; ++d) {  // toward higher squares: cap = lowest ray square outside the fill
-            const uint64_t ray = ray_of(d);
-            const uint64_t y = ray & ~t[d];
-            // ray & ((y & -y) - 1) == ray & t & (y - 1): one 3-input AND per dword
-            f |= and3_64(ray, t[d], y - 1ull);
-        }
-        // toward lower squares on the board turned by 180 degrees (square s ->
-        // NN-1-s, OneWord::turn180): the ray runs toward higher squares there,
-        // so the same lowest-bit form applies to the turned fill; one turn of
-        // the or-ed runs at the end.  The turned rays are tabled under the
-        // unturned square (the same address as the other four)
-        uint64_t g = 0;
-#pragma unroll
-        for (int d = 4; d < 8; ++d) {
-            const uint64_t ray = ray_of(d);
-            const uint64_t tt = OneWord<N>::turn180(t[d]);
-            const uint64_t y = ray & ~tt;
-            g |= and3_64(ray, tt, y - 1ull);
-        }
-        f |= OneWord<N>::turn180(g);
         BB<1> out;
-        out.w[0] = f;
+        out.w[0] = OneWord<N>::flip_fills(t, a);
         return out;
     }
     // GreedyPolicy from the fills of the side to move (bitboard.hpp OneWord::greedy)
@@ -362,6 +336,7 @@ struct FillsW {
     static constexpr int W = Geo<N>::W;
     static constexpr int LANES = 1;
     static constexpr int RAY_WORDS = 8 * N * N * W;
+    static constexpr bool FLIP_ANY = false;  // flip() reads its table at a
     const BB<W>* rays;
     mutable BB<W> t[8];
     __device__ __forceinline__ FillsW(int, const uint64_t* lds) : rays(reinterpret_cast<const BB<W>*>(lds)) {}
@@ -389,12 +364,6 @@ struct FillsW {
     }
 };
 
-// does the engine read the ray tables of the directions toward lower squares turned?
-template <typename Eng>
-struct turned_rays : std::false_type {};
-template <int N>
-struct turned_rays<Fills<N>> : std::true_type {};
-
 template <typename Eng>
 struct is_fills_w : std::false_type {};
 template <int N>
@@ -413,6 +382,7 @@ struct Quartet {
     static_assert(Geo<N>::W == 1, "Quartet engine is for one-word boards (N <= 8)");
     static constexpr int LANES = 4;
     static constexpr int RAY_WORDS = 8 * 64;
+    static constexpr bool FLIP_ANY = true;  // flip() reads its 64-entry tables at any a below 64
     static constexpr uint64_t BD = Geo<N>::BOARD.w[0], IN = Geo<N>::INNER.w[0];
     const uint64_t* rays;  // this lane's "up" table; its "down" table is 4 * 64 words further
     uint32_t sh;           // axis shift: 1, N, N + 1, N - 1
@@ -557,7 +527,7 @@ __device__ __forceinline__ void step_lane(Lane<N>& s, int a, uint32_t flags, int
     const bool tw = (s.meta & M_TURN_WHITE) != 0;
     BB<W> P = pick(tw, s.white, s.black);
     BB<W> O = pick(tw, s.black, s.white);
-    if constexpr (PICKED && Eng::RAY_WORDS > 0 && W == 1) {
+    if constexpr (PICKED && Eng::FLIP_ANY && W == 1) {
         const bool valid = a >= 0;
         const uint64_t m = valid ? 1ull << (a & 63) : 0ull;
         const uint64_t f = eng.flip(P, O, a & 63).w[0] & (0ull - (uint64_t)valid);
@@ -918,7 +888,7 @@ __global__ __launch_bounds__(BLOCK) void k_play(uint64_t* __restrict__ boards, u
     ply0 += *rng.ply_off;  // graph-region offset (oth_graph_end); 0 eagerly
     __shared__ __attribute__((aligned(16))) uint64_t lds_rays[Eng::RAY_WORDS > 0 ? Eng::RAY_WORDS : 1];
     if constexpr (is_fills_w<Eng>::value) Eng::fill(lds_rays);
-    else if constexpr (Eng::RAY_WORDS > 0) fill_rays<N, turned_rays<Eng>::value>(lds_rays);
+    else if constexpr (Eng::RAY_WORDS > 0) fill_rays<N, false>(lds_rays);  // (Quartet)
     const int gt = blockIdx.x * BLOCK + threadIdx.x;
     const int e = gt / Eng::LANES;
     const Eng eng(gt % Eng::LANES, lds_rays);
@@ -1044,7 +1014,7 @@ __device__ __forceinline__ void tally_from_signs(uint32_t s, uint32_t g, uint32_
 }
 // FILL: independent work (the next Philox block) run after the opponent's scan
 // and pinned there, so that it shares the ply's first scheduling region with the
-// pick, the ray-table loads, the flips and the scan
+// pick, the flips and the scan
 template <int N, int POLICY = OTH_POLICY_RANDOM, bool OPEN = true, typename Eng = Fills<N>, typename FILL = NoFill>
 __device__ __forceinline__ void play_rand_fast(uint64_t& M, uint64_t& O, uint64_t& L, uint32_t& meta,
                                                const Eng& eng, uint32_t u, uint32_t flags, const Rng& rng,
@@ -1076,10 +1046,7 @@ __device__ __forceinline__ void play_rand_fast(uint64_t& M, uint64_t& O, uint64_
     const uint64_t m = 1ull << a;
     BB<1> dummy;
     dummy.w[0] = 0;
-    constexpr bool RAYS_FIRST = POLICY != OTH_POLICY_RANDOM || N != 8;
-    uint64_t f;  // update_board (othello.py:391-410)
-    if constexpr (std::is_same<Eng, Fills<N>>::value) f = eng.template flip<RAYS_FIRST>(dummy, dummy, a).w[0];
-    else f = eng.flip(dummy, dummy, a).w[0];
+    const uint64_t f = eng.flip(dummy, dummy, a).w[0];  // update_board (othello.py:391-410)
     const uint64_t Mn = M | f | m, On = O & ~f;
     const bool full = (Mn | On) == BD;  // :425-426
     if constexpr (POLICY == OTH_POLICY_RANDOM) {
@@ -1191,10 +1158,12 @@ __device__ __forceinline__ void play_rand_fast(uint64_t& M, uint64_t& O, uint64_
     }
 }
 
-// tables: the handle's ray + sel8 tables (oth_env::rays, k_fill_rays), copied into
-// LDS by one 16-byte and one 8-byte load per thread, issued with the board's loads
-// (against building them per block: greedy 10-ply launches 1.85 -> 1.80 us per
-// ply, random 100-ply 0.679 -> 0.678; profiles/r04/b/)
+// tables: the handle's ray + sel8 tables (oth_env::rays, k_fill_rays); the sel8
+// table, SEL8_AT words in, is copied into LDS by one 8-byte load per thread,
+// issued with the board's loads (against building it per block: greedy 10-ply
+// launches 1.85 -> 1.80 us per ply, random 100-ply 0.679 -> 0.678;
+// profiles/r04/b/).  The ray table before it is not read here (Fills<N>::flip).
+constexpr int SEL8_AT = 8 * 64;  // launch.hpp RAY_TABLE_WORDS
 template <int N, int POLICY = OTH_POLICY_RANDOM>
 __global__ __launch_bounds__(BLOCK) void k_play_rand(uint64_t* __restrict__ boards, uint16_t* __restrict__ meta,
                                                      uint64_t* __restrict__ legal, int E, uint32_t flags, int plies,
@@ -1203,23 +1172,20 @@ __global__ __launch_bounds__(BLOCK) void k_play_rand(uint64_t* __restrict__ boar
                                                      unsigned long long* __restrict__ wdl, Rng rng, uint64_t ply0,
                                                      const uint64_t* __restrict__ tables) {
     static_assert(Geo<N>::W == 1, "one-word boards");
-    static_assert(BLOCK == 256 && Fills<N>::RAY_WORDS == 2 * BLOCK, "two ray words and one sel8 word a thread");
+    static_assert(BLOCK == 256, "one sel8 word a thread");
     ply0 += *rng.ply_off;  // graph-region offset (oth_graph_end); 0 eagerly
-    __shared__ __attribute__((aligned(16))) uint64_t lds_rays[Fills<N>::RAY_WORDS];
     __shared__ __attribute__((aligned(16))) uint64_t lds_sel[256];
     const uint8_t* sel8 = reinterpret_cast<const uint8_t*>(lds_sel);
     const int e = blockIdx.x * BLOCK + threadIdx.x;
     Lane<N> s;
-    const ulonglong2 tr = reinterpret_cast<const ulonglong2*>(tables)[threadIdx.x];
-    const uint64_t ts = tables[Fills<N>::RAY_WORDS + threadIdx.x];
+    const uint64_t ts = tables[SEL8_AT + threadIdx.x];
     if (e < E) load_lane<N>(s, boards, meta, legal, e);
-    reinterpret_cast<ulonglong2*>(lds_rays)[threadIdx.x] = tr;
     lds_sel[threadIdx.x] = ts;
     __syncthreads();
     uint32_t cb = 0, cd = 0, cw = 0;
     if (e < E) {
         const uint32_t id = rng.id_base + (uint32_t)e;
-        const Fills<N> eng(0, lds_rays);
+        const Fills<N> eng(0, nullptr);
         const bool tw0 = (s.meta & M_TURN_WHITE) != 0;
         uint64_t M = tw0 ? s.white.w[0] : s.black.w[0];
         uint64_t O = tw0 ? s.black.w[0] : s.white.w[0];

@@ -192,7 +192,8 @@ int launch_play(oth_env* env, int policy, int n_plies, int32_t* actions, int32_t
     return with_policy(policy, [&](auto PC) {
         constexpr int POL = decltype(PC)::value;
         // random and greedy play: the fills engines (flips from the legal scan's
-        // fills and a ray table in LDS; FillsW's BB<W> table of 16x16 boards is 64 KiB);
+        // fills and shifted ray constants on one-word boards, a ray table in LDS above;
+        // FillsW's BB<W> table of 16x16 boards is 64 KiB);
         // MaxiMin: Kogge-Stone flips (Solo) inside its search
         if constexpr (Geo<N>::W == 1 && (POL == OTH_POLICY_RANDOM || POL == OTH_POLICY_GREEDY)) {
             launch_k_play<N, POL, Fills<N>>(1, env, policy, n_plies, actions, rewards, dones, ply0, st);

@@ -17,6 +17,8 @@
 using namespace oth;
 using namespace oth_dev;
 
+static_assert(SEL8_AT == RAY_TABLE_WORDS, "k_play_rand reads the sel8 table behind the handle's ray table");
+
 namespace oth_host {
 
 template <int N, int POL>

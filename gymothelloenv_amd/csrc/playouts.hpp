@@ -24,9 +24,10 @@ namespace oth_dev {
 constexpr int PLAYOUT_SLOTS = 256;      // LDS counter rows: boards of a ROOT group, squares of a MOVES board
 constexpr int PLAYOUT_MAX_PLIES = 256;  // > N*N - 4 + 1: every ply after the first places a disc
 
-// the play engine per board size: flips from the legal scan's fills and LDS
-// ray tables where the tables leave room for the counters (one- and two-word
-// boards), Kogge-Stone flips without tables for three and four words
+// the play engine per board size: flips from the legal scan's fills and rays
+// (shifted constants on one-word boards, an LDS ray table on two-word boards,
+// where it leaves room for the counters), Kogge-Stone flips without tables for
+// three and four words
 template <int N>
 using PlayoutEng = std::conditional_t<Geo<N>::W == 1, Fills<N>, std::conditional_t<Geo<N>::W == 2, FillsW<N>, Solo<N>>>;
 
@@ -46,16 +47,15 @@ __global__ __launch_bounds__(BLOCK) void k_playouts(const uint64_t* __restrict__
                                                     const uint64_t* __restrict__ tables) {
     using Eng = PlayoutEng<N>;
     constexpr int W = Geo<N>::W, NN = N * N;
-    static_assert(BLOCK == 256 && NN <= PLAYOUT_SLOTS, "one counter row per square, two ray words a thread");
+    static_assert(BLOCK == 256 && NN <= PLAYOUT_SLOTS, "one counter row per square, one sel8 word a thread");
     __shared__ __attribute__((aligned(16))) uint64_t lds_rays[Eng::RAY_WORDS > 0 ? Eng::RAY_WORDS : 1];
     __shared__ __attribute__((aligned(16))) uint64_t lds_sel[256];
     __shared__ int cnt[PLAYOUT_SLOTS * 4];  // per row {wins, draws, losses, score}
     const uint8_t* sel8 = reinterpret_cast<const uint8_t*>(lds_sel);
     const int tid = threadIdx.x;
     for (int i = tid; i < PLAYOUT_SLOTS * 4; i += BLOCK) cnt[i] = 0;
-    if constexpr (W == 1) {  // the handle's ray + sel8 tables (k_fill_rays), as k_play_rand
-        reinterpret_cast<ulonglong2*>(lds_rays)[tid] = reinterpret_cast<const ulonglong2*>(tables)[tid];
-        lds_sel[tid] = tables[Fills<N>::RAY_WORDS + tid];
+    if constexpr (W == 1) {  // the handle's sel8 table (k_fill_rays), as k_play_rand
+        lds_sel[tid] = tables[SEL8_AT + tid];
         __syncthreads();
     } else if constexpr (W == 2) {
         lds_sel[tid] = sel8_word((uint32_t)tid);
@@ -126,7 +126,7 @@ __global__ __launch_bounds__(BLOCK) void k_playouts(const uint64_t* __restrict__
                     const uint64_t keep = 0ull - (uint64_t)valid;
                     BB<1> dummy;
                     dummy.w[0] = 0;
-                    const uint64_t fl = eng.template flip<N != 8>(dummy, dummy, pa).w[0] & keep;  // update_board
+                    const uint64_t fl = eng.flip(dummy, dummy, pa).w[0] & keep;  // update_board
                     const uint64_t mv = (1ull << pa) & keep;
                     BB<1> pb, ob;
                     pb.w[0] = O & ~fl;       // the next mover

@@ -62,6 +62,7 @@ def main():
         "valu_insts_per_launch": c.get("SQ_INSTS_VALU"),
         "salu_insts_per_launch": c.get("SQ_INSTS_SALU"),
         "lds_insts_per_launch": c.get("SQ_INSTS_LDS"),
+        "lds_bank_conflict_cycles_per_launch": c.get("SQ_LDS_BANK_CONFLICT"),
         "waves_per_launch": c.get("SQ_WAVES"),
         "wave_cycles_quad": c.get("SQ_WAVE_CYCLES"),
         "wait_any_quad": c.get("SQ_WAIT_ANY"),
