@@ -10,11 +10,9 @@
 #include <string>
 #include <type_traits>
 
-#include "device.hpp"
 #include "launch.hpp"
 
 using namespace oth;
-using namespace oth_dev;
 using namespace oth_host;
 
 namespace oth_host {
@@ -258,7 +256,7 @@ int oth_create(int32_t n_envs, int32_t board_size, uint32_t flags, uint64_t seed
     const size_t ctr_bytes = (size_t)OTH_GRAPH_SLOTS * 2 * sizeof(uint64_t);
     if (err == hipSuccess) err = hipMalloc((void**)&env->ctr_slots, ctr_bytes);
     if (err == hipSuccess) err = hipMemset(env->ctr_slots, 0, ctr_bytes);
-    if (err == hipSuccess && env->W == 1) err = hipMalloc((void**)&env->rays, TABLE_WORDS * sizeof(uint64_t));
+    if (err == hipSuccess && env->W == 1) err = hipMalloc((void**)&env->tables, TABLE_WORDS * sizeof(uint64_t));
     env->cur_off = env->ctr_slots;
     env->graph_slot = 0;
     env->slots_used = 1;
@@ -289,7 +287,7 @@ int oth_destroy(oth_env* env) {
     if (env->wdl) (void)hipFree(env->wdl);
     if (env->wdl_vs) (void)hipFree(env->wdl_vs);
     if (env->ctr_slots) (void)hipFree(env->ctr_slots);
-    if (env->rays) (void)hipFree(env->rays);
+    if (env->tables) (void)hipFree(env->tables);
     if (env->rec_host) (void)hipHostFree(env->rec_host);
     delete env;
     return OTH_OK;
@@ -638,7 +636,7 @@ int oth_set_state(oth_env* env, const uint64_t* boards, const uint16_t* meta, co
 
 int oth_set_player_turn(oth_env* env, int32_t turn, const uint8_t* mask, oth_stream_t stream) {
     OTH_CHECK_ENV(env);
-    if (turn != WHITE_DISK && turn != BLACK_DISK) return fail(OTH_EINVAL, "turn must be +1 or -1");
+    if (turn != 1 && turn != -1) return fail(OTH_EINVAL, "turn must be +1 or -1");
     return with_n(env->n, [&](auto NC) {
         return launch_set_turn<decltype(NC)::value>(env, turn, mask, (hipStream_t)stream);
     });

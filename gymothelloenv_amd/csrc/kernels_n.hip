@@ -49,12 +49,47 @@ struct ObsOut {
     int dtype = 0;
     void* out = nullptr;
 };
-// obs_tail's quad stores need N*N % 4 == 0 and an output aligned to 4 elements
+// bytes of an observation element (OTH_I8 .. OTH_BF16; 0 for any other dtype)
+int obs_elem_size(int dtype) {
+    static const int esize[6] = {1, 4, 8, 4, 8, 2};
+    return dtype >= OTH_I8 && dtype <= OTH_BF16 ? esize[dtype] : 0;
+}
+// the vector stores of obs_stream (k_observe_w, obs_tail) need N*N % 4 == 0 and
+// an output aligned to their unit (obs_align)
 template <int N>
 bool obs_fusable(int dtype, const void* out) {
-    static const int esize[6] = {1, 4, 8, 4, 8, 2};
-    return (N * N) % 4 == 0 && dtype >= OTH_I8 && dtype <= OTH_BF16 &&
-           (uintptr_t)out % obs_align(N * N, esize[dtype]) == 0;
+    const int esize = obs_elem_size(dtype);
+    return (N * N) % 4 == 0 && esize && (uintptr_t)out % obs_align(N * N, esize) == 0;
+}
+
+// Compile-time layout for a runtime id (OTH_OBS_*)
+template <typename Fn>
+void with_layout(int layout, Fn&& fn) {
+    switch (layout) {
+        case OTH_OBS_BOARD: return fn(std::integral_constant<int, OTH_OBS_BOARD>{});
+        case OTH_OBS_BOARD_LEGAL: return fn(std::integral_constant<int, OTH_OBS_BOARD_LEGAL>{});
+        case OTH_OBS_MAKE_STATE: return fn(std::integral_constant<int, OTH_OBS_MAKE_STATE>{});
+        case OTH_OBS_ABSOLUTE: return fn(std::integral_constant<int, OTH_OBS_ABSOLUTE>{});
+        default: return fn(std::integral_constant<int, OTH_OBS_LEGAL>{});
+    }
+}
+
+template <typename Fn>
+void with_bool(bool b, Fn&& fn) {
+    if (b) fn(std::true_type{});
+    else fn(std::false_type{});
+}
+
+// The single-ply kernels of one-word boards (ply.hpp): launches of at most
+// OTH_PLY_MATH_MAX_E boards compute their rays (RAYS_MATH: one wave per SIMD runs a
+// latency-bound chain, 65,536 boards 3.37 -> 3.11 us per ply), larger ones stage the
+// handle's up rays in LDS (RAYS_HALF); the figures are with the constants in ply.hpp
+template <typename K, typename A>
+void launch_ply(oth_env* env, K math, K half, A* actions, int32_t* rewards, uint8_t* dones, uint64_t ply,
+                hipStream_t st) {
+    launch_k(env->E <= OTH_PLY_MATH_MAX_E ? math : half, dim3(grid_for(env->E)), dim3(BLOCK), 0, st, env->boards,
+             env->meta, env->legal, env->E, env->flags, actions, rewards, dones, env->wdl, env->tables, rng_of(env),
+             ply);
 }
 
 }  // namespace
@@ -66,11 +101,11 @@ int launch_reset(oth_env* env, const uint8_t* mask, hipStream_t st) {
     return after_launch("oth_reset");
 }
 
-// oth_create for one-word boards: the single-ply kernels' ray table
+// oth_create for one-word boards: the handle's tables (tables.hpp)
 template <int N>
 int launch_fill_rays(oth_env* env, hipStream_t st) {
     if constexpr (Geo<N>::W == 1) {
-        launch_k(k_fill_rays<N>, dim3(1), dim3(BLOCK), 0, st, env->rays);
+        launch_k(k_fill_rays<N>, dim3(1), dim3(BLOCK), 0, st, env->tables);
         return after_launch("oth_create: ray table");
     }
     return OTH_OK;
@@ -79,15 +114,8 @@ int launch_fill_rays(oth_env* env, hipStream_t st) {
 template <int N>
 int launch_step(oth_env* env, const int32_t* actions, int32_t* rewards, uint8_t* dones, uint64_t ply,
                 hipStream_t st) {
-    if constexpr (Geo<N>::W == 1) {  // the single-ply kernel (ply.hpp)
-        if (env->E <= OTH_PLY_MATH_MAX_E)
-            launch_k((k_ply_step<N, RAYS_MATH>), dim3(grid_for(env->E)), dim3(BLOCK), 0, st, env->boards,
-                     env->meta, env->legal, env->E, env->flags, actions, rewards, dones, env->wdl, env->rays,
-                     rng_of(env), ply);
-        else
-            launch_k((k_ply_step<N, RAYS_HALF>), dim3(grid_for(env->E)), dim3(BLOCK), 0, st,
-                     env->boards, env->meta, env->legal, env->E, env->flags, actions, rewards, dones,
-                     env->wdl, env->rays, rng_of(env), ply);
+    if constexpr (Geo<N>::W == 1) {
+        launch_ply(env, k_ply_step<N, RAYS_MATH>, k_ply_step<N, RAYS_HALF>, actions, rewards, dones, ply, st);
         return after_launch("oth_step");
     }
     launch_k(k_step<N>, dim3(grid_for(env->E)), dim3(BLOCK), 0, st, env->boards, env->meta, env->legal,
@@ -134,56 +162,46 @@ int launch_step_observe(oth_env* env, const int32_t* actions, int32_t* rewards, 
     return launch_observe<N>(env, layout, dtype, obs, st);
 }
 
-// k_play with the REC specialisation where all per-ply outputs are stored
-// (random / greedy only, to bound the number of maximin instantiations).
+// oth_step_policy's kernel for a policy and an engine, each rule once:
+//   * one random ply of one-word boards: the single-ply kernel (launch_ply), any flags;
+//   * random or greedy play with every per-ply output stored and auto-reset -- the
+//     benchmark configuration -- on the fills engines: k_play_rand (one-word boards,
+//     both policies) and k_play_rand_w (multi-word boards, random), results as k_play's;
+//     two-word boards in play_rand_n.hip's max-ILP unit (10x10 +5 %), larger ones
+//     here (12x12 -4 % there);
+//   * else k_play, with its REC specialisation where every per-ply output is stored
+//     (random / greedy only, to bound the number of maximin instantiations).
 template <int N, int POL, typename Eng>
-void launch_k_play(int lanes_per_board, oth_env* env, int policy, int n_plies, int32_t* actions, int32_t* rewards,
-                   uint8_t* dones, uint64_t ply0, hipStream_t st) {
-    const dim3 grid(grid_for((long long)lanes_per_board * env->E)), block(BLOCK);
-    if constexpr (POL == OTH_POLICY_RANDOM && Geo<N>::W == 1) {
-        if (n_plies == 1) {  // one ply per launch: the single-ply kernel (ply.hpp), any flags
-            if (env->E <= OTH_PLY_MATH_MAX_E)
-                launch_k((k_ply_rand<N, RAYS_MATH>), dim3(grid_for(env->E)), block, 0, st, env->boards,
-                         env->meta, env->legal, env->E, env->flags, actions, rewards, dones, env->wdl,
-                         env->rays, rng_of(env), ply0);
+void launch_k_play(oth_env* env, int policy, int n_plies, int32_t* actions, int32_t* rewards, uint8_t* dones,
+                   uint64_t ply0, hipStream_t st) {
+    constexpr bool RANDOM = POL == OTH_POLICY_RANDOM, GREEDY = POL == OTH_POLICY_GREEDY;
+    const dim3 grid(grid_for(env->E)), block(BLOCK);
+    const bool rec = actions && rewards && dones;
+    const bool fast = rec && (env->flags & OTH_AUTO_RESET);
+    auto play = [&](auto k) {
+        launch_k(k, grid, block, 0, st, env->boards, env->meta, env->legal, env->E, env->flags, n_plies, actions,
+                 rewards, dones, env->wdl, rng_of(env, policy), ply0);
+    };
+    if constexpr (RANDOM && Geo<N>::W == 1) {
+        if (n_plies == 1)
+            return launch_ply(env, k_ply_rand<N, RAYS_MATH>, k_ply_rand<N, RAYS_HALF>, actions, rewards, dones, ply0,
+                              st);
+    }
+    if constexpr ((RANDOM || GREEDY) && std::is_same<Eng, Fills<N>>::value) {
+        if (fast) return launch_play_rand<N, POL>(env, n_plies, actions, rewards, dones, ply0, st);
+    }
+    if constexpr (RANDOM && std::is_same<Eng, FillsW<N>>::value) {
+        if (fast) {
+            if constexpr (Geo<N>::W == 2)
+                return launch_play_rand<N, POL>(env, n_plies, actions, rewards, dones, ply0, st);
             else
-                launch_k((k_ply_rand<N, RAYS_HALF>), dim3(grid_for(env->E)), block, 0, st,
-                         env->boards, env->meta, env->legal, env->E, env->flags, actions, rewards, dones,
-                         env->wdl, env->rays, rng_of(env), ply0);
-            return;
+                return play(k_play_rand_w<N>);
         }
     }
-    if constexpr (POL == OTH_POLICY_RANDOM && std::is_same<Eng, Fills<N>>::value) {
-        if (actions && rewards && dones && (env->flags & OTH_AUTO_RESET)) {
-            launch_play_rand<N, OTH_POLICY_RANDOM>(env, n_plies, actions, rewards, dones, ply0, st);  // play_rand_n.hip
-            return;
-        }
+    if constexpr (RANDOM || GREEDY) {
+        if (rec) return play(k_play<N, POL, Eng, true>);
     }
-    if constexpr (POL == OTH_POLICY_GREEDY && std::is_same<Eng, Fills<N>>::value) {
-        if (actions && rewards && dones && (env->flags & OTH_AUTO_RESET)) {
-            launch_play_rand<N, OTH_POLICY_GREEDY>(env, n_plies, actions, rewards, dones, ply0, st);  // play_rand_n.hip
-            return;
-        }
-    }
-    if constexpr (POL == OTH_POLICY_RANDOM && std::is_same<Eng, FillsW<N>>::value) {
-        if (actions && rewards && dones && (env->flags & OTH_AUTO_RESET)) {
-            if constexpr (Geo<N>::W == 2)  // the max-ILP unit (play_rand_n.hip): 10x10 +5 %, 12x12 -4 %
-                launch_play_rand<N, OTH_POLICY_RANDOM>(env, n_plies, actions, rewards, dones, ply0, st);
-            else
-                launch_k((k_play_rand_w<N>), grid, block, 0, st, env->boards, env->meta, env->legal, env->E,
-                         env->flags, n_plies, actions, rewards, dones, env->wdl, rng_of(env, policy), ply0);
-            return;
-        }
-    }
-    if constexpr (POL == OTH_POLICY_RANDOM || POL == OTH_POLICY_GREEDY) {
-        if (actions && rewards && dones) {
-            launch_k((k_play<N, POL, Eng, true>), grid, block, 0, st, env->boards, env->meta, env->legal,
-                     env->E, env->flags, n_plies, actions, rewards, dones, env->wdl, rng_of(env, policy), ply0);
-            return;
-        }
-    }
-    launch_k((k_play<N, POL, Eng, false>), grid, block, 0, st, env->boards, env->meta, env->legal, env->E,
-             env->flags, n_plies, actions, rewards, dones, env->wdl, rng_of(env, policy), ply0);
+    play(k_play<N, POL, Eng, false>);
 }
 
 template <int N>
@@ -196,11 +214,11 @@ int launch_play(oth_env* env, int policy, int n_plies, int32_t* actions, int32_t
         // FillsW's BB<W> table of 16x16 boards is 64 KiB);
         // MaxiMin: Kogge-Stone flips (Solo) inside its search
         if constexpr (Geo<N>::W == 1 && (POL == OTH_POLICY_RANDOM || POL == OTH_POLICY_GREEDY)) {
-            launch_k_play<N, POL, Fills<N>>(1, env, policy, n_plies, actions, rewards, dones, ply0, st);
+            launch_k_play<N, POL, Fills<N>>(env, policy, n_plies, actions, rewards, dones, ply0, st);
         } else if constexpr (Geo<N>::W > 1 && (POL == OTH_POLICY_RANDOM || POL == OTH_POLICY_GREEDY)) {
-            launch_k_play<N, POL, FillsW<N>>(1, env, policy, n_plies, actions, rewards, dones, ply0, st);
+            launch_k_play<N, POL, FillsW<N>>(env, policy, n_plies, actions, rewards, dones, ply0, st);
         } else {
-            launch_k_play<N, POL, Solo<N>>(1, env, policy, n_plies, actions, rewards, dones, ply0, st);
+            launch_k_play<N, POL, Solo<N>>(env, policy, n_plies, actions, rewards, dones, ply0, st);
         }
         return after_launch("oth_step_policy");
     });
@@ -209,6 +227,12 @@ int launch_play(oth_env* env, int policy, int n_plies, int32_t* actions, int32_t
 // with the observation tail: lane quads (16 boards a wave, the store loop's best
 // shape) up to this many boards.  8x8, make_state f32, graphed: 32,768 boards
 // 14.27 -> 12.34 us per ply on quads; 65,536 17.37 -> 17.85 (profiles/r05/c/ab_ss_obs*.json)
+#ifndef OTH_SS_QUAD_MAX_E
+#define OTH_SS_QUAD_MAX_E 16384  // oth_sample_step on lane quads up to this many boards: 4 lanes each fill at most 1,024 waves (one per SIMD)
+#endif
+#ifndef OTH_SS_PAIR_W_MAX_E
+#define OTH_SS_PAIR_W_MAX_E 32768  // two-word boards whose rows are not float4-aligned: lane pairs up to this many boards
+#endif
 #ifndef OTH_SSO_QUAD_MAX_E
 #define OTH_SSO_QUAD_MAX_E 32768
 #endif
@@ -216,19 +240,19 @@ template <int N, int G, bool VEC, bool FULL>
 void launch_ss(oth_env* env, const float* logits, long long ld, const float* uniforms, uint64_t counter, int mode,
                int32_t* actions, float* log_probs, float* entropy, int32_t* rewards, uint8_t* dones, uint64_t ply,
                const ObsOut& ob, hipStream_t st) {
+    auto go = [&](auto k, long long lanes) {  // the three kernels share one parameter list
+        launch_k(k, dim3(grid_for(lanes)), dim3(BLOCK), 0, st, env->boards, env->meta, env->legal, env->E, env->flags,
+                 logits, ld, uniforms, counter, mode, actions, log_probs, entropy, rewards, dones, env->wdl,
+                 rng_of(env), ply, ob.layout, ob.dtype, ob.out);
+    };
     // lane quads (k_sample_step4) while the quads fill at most one wave per SIMD: latency-bound sizes,
     // where a quarter of the per-lane instruction stream wins (8x8, E = 3001: 5.67 -> 4.83 us per ply);
     // beyond, the quads' duplicated step work loses to pairs (65,536: 7.02 -> 7.45)
     // (the tally slots oth_create sizes cover the quads' grid: one slot per block)
     if constexpr (Geo<N>::W == 1) {
         const long long quad_max = ob.out ? OTH_SSO_QUAD_MAX_E : OTH_SS_QUAD_MAX_E;
-        if (env->E <= quad_max && grid_for(4LL * env->E) <= env->nslots) {
-            launch_k((k_sample_step4<N, VEC, FULL>), dim3(grid_for(4LL * env->E)), dim3(BLOCK), 0, st,
-                     env->boards, env->meta, env->legal, env->E, env->flags, logits, ld, uniforms, counter,
-                     mode, actions, log_probs, entropy, rewards, dones, env->wdl, rng_of(env), ply, ob.layout, ob.dtype,
-                     ob.out);
-            return;
-        }
+        if (env->E <= quad_max && grid_for(4LL * env->E) <= env->nslots)
+            return go(k_sample_step4<N, VEC, FULL>, 4LL * env->E);
     }
     // lane pairs (k_sample_step2) for 7x7 and 8x8: 8x8 7.77 -> 7.22 us per ply graphed (-8.5 % with
     // log-probs); 6x6 loses (5.1 -> 6.0: the one-lane form folds the squares past N*N away)
@@ -238,20 +262,12 @@ void launch_ss(oth_env* env, const float* logits, long long ld, const float* uni
     constexpr bool PAIR1 = Geo<N>::W == 1 && N >= 7;
     constexpr bool PAIR2 = Geo<N>::W == 2;
     if constexpr (PAIR1 || PAIR2) {
-        if (PAIR1 || VEC || env->E <= OTH_SS_PAIR_W_MAX_E) {
-            launch_k((k_sample_step2<N, VEC, FULL>), dim3(grid_for(2LL * env->E)), dim3(BLOCK), 0, st,
-                     env->boards, env->meta, env->legal, env->E, env->flags, logits, ld, uniforms, counter,
-                     mode, actions, log_probs, entropy, rewards, dones, env->wdl, rng_of(env), ply, ob.layout, ob.dtype,
-                     ob.out);
-            return;
-        }
+        if (PAIR1 || VEC || env->E <= OTH_SS_PAIR_W_MAX_E) return go(k_sample_step2<N, VEC, FULL>, 2LL * env->E);
     }
     // one lane samples one board (oth_ms::sample_lane) for boards of <= 2 words
     constexpr bool ONE = Geo<N>::W <= 2;
     const long long lanes = ONE ? (long long)env->E : ((long long)env->E + G - 1) / G * G;
-    launch_k((k_sample_step<N, G, VEC, FULL, ONE>), dim3(grid_for(lanes)), dim3(BLOCK), 0, st, env->boards,
-             env->meta, env->legal, env->E, env->flags, logits, ld, uniforms, counter, mode, actions,
-             log_probs, entropy, rewards, dones, env->wdl, rng_of(env), ply, ob.layout, ob.dtype, ob.out);
+    go(k_sample_step<N, G, VEC, FULL, ONE>, lanes);
 }
 
 // the sampler's lanes per board: k_masked's choice for the board's word count
@@ -268,17 +284,12 @@ int launch_sample_step(oth_env* env, const float* logits, long long ld, const fl
     // write `obs`; else a k_observe launch after it (the same values)
     const bool fuse = obs && obs_fusable<N>(obs_dtype, obs);
     const ObsOut ob = fuse ? ObsOut{obs_layout, obs_dtype, obs} : ObsOut{};
-    if (vec) {
-        if (full) launch_ss<N, G, true, true>(env, logits, ld, uniforms, counter, base, actions, log_probs, entropy,
-                                              rewards, dones, ply, ob, st);
-        else launch_ss<N, G, true, false>(env, logits, ld, uniforms, counter, base, actions, log_probs, entropy,
-                                          rewards, dones, ply, ob, st);
-    } else {
-        if (full) launch_ss<N, G, false, true>(env, logits, ld, uniforms, counter, base, actions, log_probs,
-                                               entropy, rewards, dones, ply, ob, st);
-        else launch_ss<N, G, false, false>(env, logits, ld, uniforms, counter, base, actions, log_probs, entropy,
-                                           rewards, dones, ply, ob, st);
-    }
+    with_bool(vec, [&](auto VC) {
+        with_bool(full, [&](auto FC) {
+            launch_ss<N, G, decltype(VC)::value, decltype(FC)::value>(env, logits, ld, uniforms, counter, base, actions,
+                                                                      log_probs, entropy, rewards, dones, ply, ob, st);
+        });
+    });
     const int rc = after_launch("oth_sample_step");
     if (rc || !obs || fuse) return rc;
     return launch_observe<N>(env, obs_layout, obs_dtype, obs, st);
@@ -376,7 +387,7 @@ int launch_legal_moves(int n, const uint64_t* mover, const uint64_t* opp, uint64
 #endif
 template <int N, int LAYOUT, typename T>
 constexpr int obs_large_bpw() {
-    constexpr int want = OTH_OBS_LARGE_REGION / (obs_planes<LAYOUT>() * N * N * (int)sizeof(T));
+    constexpr int want = OTH_OBS_LARGE_REGION / (obs_planes(LAYOUT) * N * N * (int)sizeof(T));
     return want >= 64 ? 64 : (want >= 32 ? 32 : (want >= 16 ? 16 : (want >= 8 ? 8 : 4)));
 }
 
@@ -384,26 +395,18 @@ constexpr int obs_large_bpw() {
 // BPW0: boards per wave, or 0 for the layout's 4-KiB regions (obs_large_bpw)
 template <int N, typename T, int BPW0>
 void launch_observe_bpw(oth_env* env, int layout, T* o, hipStream_t st) {
-    auto go = [&](auto LC) {
+    with_layout(layout, [&](auto LC) {
         constexpr int LAY = decltype(LC)::value;
         constexpr int BPW = BPW0 ? BPW0 : obs_large_bpw<N, LAY, T>();
         const dim3 gw(grid_for(((long long)env->E + BPW - 1) / BPW * 64));
         launch_k((k_observe_w<N, LAY, T, BPW>), gw, dim3(BLOCK), 0, st, env->boards, env->meta, env->legal, env->E,
                  o);
-    };
-    switch (layout) {
-        case OTH_OBS_BOARD: go(std::integral_constant<int, OTH_OBS_BOARD>{}); break;
-        case OTH_OBS_BOARD_LEGAL: go(std::integral_constant<int, OTH_OBS_BOARD_LEGAL>{}); break;
-        case OTH_OBS_MAKE_STATE: go(std::integral_constant<int, OTH_OBS_MAKE_STATE>{}); break;
-        case OTH_OBS_ABSOLUTE: go(std::integral_constant<int, OTH_OBS_ABSOLUTE>{}); break;
-        default: go(std::integral_constant<int, OTH_OBS_LEGAL>{}); break;
-    }
+    });
 }
 template <int N, typename T>
 void launch_observe_w(oth_env* env, int layout, void* out, hipStream_t st) {
     T* o = static_cast<T*>(out);
-    const int planes = layout == OTH_OBS_BOARD_LEGAL ? 2 : (layout == OTH_OBS_MAKE_STATE ? 4 : 1);
-    const long long bytes = (long long)env->E * planes * N * N * (long long)sizeof(T);
+    const long long bytes = (long long)env->E * obs_planes(layout) * N * N * (long long)sizeof(T);
     if (env->E < OTH_OBS_SMALL_E) launch_observe_bpw<N, T, 16>(env, layout, o, st);
     else if (bytes <= OTH_OBS_REGION_MIN_BYTES) launch_observe_bpw<N, T, 64>(env, layout, o, st);
     else launch_observe_bpw<N, T, 0>(env, layout, o, st);
@@ -411,13 +414,10 @@ void launch_observe_w(oth_env* env, int layout, void* out, hipStream_t st) {
 
 template <int N>
 int launch_observe(oth_env* env, int layout, int dtype, void* out, hipStream_t st) {
-    const int planes = layout == OTH_OBS_BOARD_LEGAL ? 2 : (layout == OTH_OBS_MAKE_STATE ? 4 : 1);
-    const long long total = (long long)env->E * planes * N * N;
-    static const int esize[6] = {1, 4, 8, 4, 8, 2};
+    const long long total = (long long)env->E * obs_planes(layout) * N * N;
     if constexpr ((N * N) % 4 == 0) {
-        // vector stores need a 4-element-aligned base and 32-bit quad indices
-        if (dtype >= OTH_I8 && dtype <= OTH_BF16 && (uintptr_t)out % obs_align(N * N, esize[dtype]) == 0 &&
-            total / 4 < (1ll << 31)) {
+        // vector stores need an aligned base (obs_fusable) and 32-bit quad indices
+        if (obs_fusable<N>(dtype, out) && total / 4 < (1ll << 31)) {
             switch (dtype) {
                 case OTH_I8: launch_observe_w<N, int8_t>(env, layout, out, st); break;
                 case OTH_I32: launch_observe_w<N, int32_t>(env, layout, out, st); break;

@@ -1,6 +1,6 @@
 // masked.hpp -- the masked categorical's device code,
 // shared by k_masked (masked.hip) and the fused sample-and-step kernel
-// (device.hpp k_sample_step): both run exactly these instructions per board,
+// (sample_step.hpp k_sample_step): both run exactly these instructions per board,
 // so the fused path's samples, log-probs and entropies are bit-identical to
 // oth_sample_actions followed by oth_step.
 //

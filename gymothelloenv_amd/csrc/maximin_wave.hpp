@@ -14,7 +14,7 @@
 // the wave wait for its deepest board's whole tree.
 #pragma once
 
-#include "device.hpp"
+#include "policy.hpp"
 
 #ifndef OTH_MM_NESTED_MAX_E
 // launches of at most this many boards at depth >= 4 take the nested subtrees

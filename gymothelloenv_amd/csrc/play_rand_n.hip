@@ -7,7 +7,7 @@
 // chains counts and occupancy does not: 8x8 0.779 -> 0.762 us per ply with
 // the next Philox block pinned in the group's first ply (profiles/r02/fi/).  The same flag on the whole library costs
 // the fused sample-and-step kernel 4 %, hence the separate unit.
-#include "device.hpp"
+#include "play.hpp"
 #include "launch.hpp"
 
 #ifndef OTH_N
@@ -16,8 +16,6 @@
 
 using namespace oth;
 using namespace oth_dev;
-
-static_assert(SEL8_AT == RAY_TABLE_WORDS, "k_play_rand reads the sel8 table behind the handle's ray table");
 
 namespace oth_host {
 
@@ -30,7 +28,7 @@ void launch_play_rand(oth_env* env, int n_plies, int32_t* actions, int32_t* rewa
     // git show 53fb080:gymothelloenv_amd/csrc/pair_play.hpp)
     if constexpr (Geo<N>::W == 1)
         launch_k((k_play_rand<N, POL>), grid, block, 0, st, env->boards, env->meta, env->legal, env->E,
-                 env->flags, n_plies, actions, rewards, dones, env->wdl, rng, ply0, env->rays);
+                 env->flags, n_plies, actions, rewards, dones, env->wdl, rng, ply0, env->tables);
     else  // random play only (k_play_rand_w)
         launch_k((k_play_rand_w<N>), grid, block, 0, st, env->boards, env->meta, env->legal, env->E,
                  env->flags, n_plies, actions, rewards, dones, env->wdl, rng, ply0);

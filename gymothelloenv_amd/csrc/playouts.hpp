@@ -17,7 +17,7 @@
 // The Philox id of a playout is a function of (global env id, square, r)
 // alone, so none of this shows in the results.
 #pragma once
-#include "device.hpp"
+#include "engines.hpp"
 
 namespace oth_dev {
 

@@ -46,10 +46,10 @@ int launch_playouts(oth_env* env, int mode, int R, uint64_t seed, uint32_t id_ke
     const dim3 grid((unsigned)(groups * B)), block(BLOCK);
     if (mode == OTH_PLAYOUT_ROOT)
         launch_k((k_playouts<N, OTH_PLAYOUT_ROOT>), grid, block, 0, st, env->boards, env->meta, env->legal, env->E, R,
-                 EPB, (int)B, key, wdl, score, split, env->rays);
+                 EPB, (int)B, key, wdl, score, split, env->tables);
     else
         launch_k((k_playouts<N, OTH_PLAYOUT_MOVES>), grid, block, 0, st, env->boards, env->meta, env->legal, env->E, R,
-                 EPB, (int)B, key, wdl, score, split, env->rays);
+                 EPB, (int)B, key, wdl, score, split, env->tables);
     if (best)  // from the finished counts (a board's playouts may be split over blocks): a launch of its own
         launch_k(k_playout_best<N>, dim3((unsigned)((E + BLOCK - 1) / BLOCK)), block, 0, st, env->meta, env->legal,
                  env->E, wdl, best);

@@ -22,7 +22,9 @@
 //     no LDS, no barrier, no atomics.
 #pragma once
 
-#include "device.hpp"
+#include "engines.hpp"
+#include "observe.hpp"
+#include "vs.hpp"
 
 namespace oth_dev {
 
@@ -46,7 +48,7 @@ constexpr int RAYS_MATH = 2, RAYS_HALF = 3, RAYS_PAIR = 4;
 #define OTH_PLY_MATH_MAX_E 65536  // single-ply launches of at most this many boards compute their rays
 #endif
 
-// RayMath (the rays of a square without a table) is in device.hpp.
+// RayMath (the rays of a square without a table) is in engines.hpp.
 
 // The run one direction flips: the ray's squares before its nearest
 // non-opponent square y0 (the lowest set bit of y = ray & ~O; all of them
@@ -67,7 +69,7 @@ __device__ __forceinline__ uint64_t capped_run(uint64_t ray, uint64_t P, uint64_
 // update_board's flips (othello.py:391-410) for a move on square a: the four
 // directions toward higher squares on the board, the four toward lower ones on
 // the board turned by 180 degrees (OneWord::turn180), where they point to
-// higher squares too.  r = rays + a, the table of fill_rays<N, true>.
+// higher squares too.  r = rays + a, the up rays (the handle's table, staged in LDS).
 template <int N, int RAYS>
 __device__ __forceinline__ uint64_t flips_rays(uint64_t P, uint64_t O, const uint64_t* __restrict__ r, int a,
                                                int h = 0) {
@@ -87,28 +89,29 @@ __device__ __forceinline__ uint64_t flips_rays(uint64_t P, uint64_t O, const uin
         const uint32_t plo = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)lo, 0xB1, 0xF, 0xF, false);
         const uint32_t phi = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)hi, 0xB1, 0xF, 0xF, false);
         return f | ((uint64_t)phi << 32 | plo);
-    }
-    uint64_t ray[8];
-    if constexpr (RAYS == RAYS_MATH) {  // the turned rays are the up rays of square NN-1-a, column N-1-c
-        const uint32_t s = (uint32_t)a & 63u, c = s % N;
-        RayMath<N>::up(s, c, ray);
-        RayMath<N>::up(RayMath<N>::turned(s), N - 1 - c, ray + 4);
     } else {
-        static_assert(RAYS == RAYS_HALF || RAYS == RAYS_PAIR, "ray source");  // (PAIR returned above)
-        const uint64_t* rt = r - (a & 63) + ((N * N - 1 - (a & 63)) & 63);  // (in the table for any a)
+        uint64_t ray[8];
+        if constexpr (RAYS == RAYS_MATH) {  // the turned rays are the up rays of square NN-1-a, column N-1-c
+            const uint32_t s = (uint32_t)a & 63u, c = s % N;
+            RayMath<N>::up(s, c, ray);
+            RayMath<N>::up(RayMath<N>::turned(s), N - 1 - c, ray + 4);
+        } else {
+            static_assert(RAYS == RAYS_HALF, "ray source");
+            const uint64_t* rt = r - (a & 63) + ((N * N - 1 - (a & 63)) & 63);  // (in the table for any a)
 #pragma unroll
-        for (int d = 0; d < 4; ++d) {
-            ray[d] = r[64 * d];
-            ray[4 + d] = rt[64 * d];
+            for (int d = 0; d < 4; ++d) {
+                ray[d] = r[64 * d];
+                ray[4 + d] = rt[64 * d];
+            }
         }
+        uint64_t f = 0, g = 0;
+#pragma unroll
+        for (int d = 0; d < 4; ++d) f |= capped_run(ray[d], P, O);
+        const uint64_t Pt = OneWord<N>::turn180(P), Ot = OneWord<N>::turn180(O);
+#pragma unroll
+        for (int d = 4; d < 8; ++d) g |= capped_run(ray[d], Pt, Ot);
+        return f | OneWord<N>::turn180(g);
     }
-    uint64_t f = 0, g = 0;
-#pragma unroll
-    for (int d = 0; d < 4; ++d) f |= capped_run(ray[d], P, O);
-    const uint64_t Pt = OneWord<N>::turn180(P), Ot = OneWord<N>::turn180(O);
-#pragma unroll
-    for (int d = 4; d < 8; ++d) g |= capped_run(ray[d], Pt, Ot);
-    return f | OneWord<N>::turn180(g);
 }
 
 
@@ -246,7 +249,7 @@ __device__ __forceinline__ void ply_body(uint64_t* __restrict__ boards, uint16_t
                                          const uint64_t* __restrict__ rays_g, Rng rng, uint64_t ply) {
     static_assert(Geo<N>::W == 1, "one-word boards");
     constexpr int NN = N * N;
-    constexpr int TABLE = RAYS == RAYS_HALF ? 4 * 64 : 0;  // words staged in LDS
+    constexpr int TABLE = RAYS == RAYS_HALF ? UP_RAY_WORDS : 0;  // words staged in LDS
     // the large launches store nontemporally (streaming, no L2 allocation): 262,144
     // boards 5.85 -> 5.50 us per ply, 1,048,576 13.32 -> 12.78; the small ones gain
     // nothing from it (profiles/r03/nt/)
@@ -261,7 +264,7 @@ __device__ __forceinline__ void ply_body(uint64_t* __restrict__ boards, uint16_t
     // all (the wave then waits only for it before its LDS store), the board's
     // loads (lanes past E load board E - 1 and store nothing), the wave's slot
     uint64_t rh;
-    if constexpr (TABLE) rh = rays_g[threadIdx.x];  // the four up directions: the table's first half
+    if constexpr (TABLE) rh = rays_g[threadIdx.x];  // the four up directions' rays
     const ulonglong2 bw = reinterpret_cast<const ulonglong2*>(boards)[e];
     uint64_t L = legal[e];
     uint32_t m = meta[e];
@@ -295,14 +298,8 @@ __device__ __forceinline__ void ply_body(uint64_t* __restrict__ boards, uint16_t
     }
     const bool ended = mine && d && !was_term;
     if (ended && (flags & OTH_AUTO_RESET)) {  // reset (othello.py:256-271), black to move
-        B = Start<N>::BLACK.w[0];
-        Wt = Start<N>::WHITE.w[0];
-        constexpr uint64_t START_MOVES = start_moves<N>();  // constant-evaluated
-        L = START_MOVES;
-        uint32_t rl = 0;
-        if (rng.init_rand > 0)
-            rl = (uint32_t)scale_index(opening_draw(rng.seed, id, ply, RNG_OPENING_AUTO), rng.init_rand / 2 + 1) * 2u;
-        m = (rl & 0xffu) << M_RAND_SHIFT;
+        start_position<N>(B, Wt, L);
+        m = reset_meta(rng.seed, id, ply, RNG_OPENING_AUTO, rng.init_rand);
     }
     if (mine) {
         if (!was_term) {
@@ -413,14 +410,8 @@ __global__ __launch_bounds__(BLOCK) void k_ply_step_obs(uint64_t* __restrict__ b
     }
     const bool ended = mine && d && !was_term;
     if (ended && (flags & OTH_AUTO_RESET)) {  // reset (othello.py:256-271), black to move
-        B = Start<N>::BLACK.w[0];
-        Wt = Start<N>::WHITE.w[0];
-        constexpr uint64_t START_MOVES = start_moves<N>();
-        L = START_MOVES;
-        uint32_t rl = 0;
-        if (rng.init_rand > 0)
-            rl = (uint32_t)scale_index(opening_draw(rng.seed, id, ply, RNG_OPENING_AUTO), rng.init_rand / 2 + 1) * 2u;
-        m = (rl & 0xffu) << M_RAND_SHIFT;
+        start_position<N>(B, Wt, L);
+        m = reset_meta(rng.seed, id, ply, RNG_OPENING_AUTO, rng.init_rand);
     }
     if (mine && h == 0) {
         if (!was_term) {
@@ -449,7 +440,7 @@ __global__ __launch_bounds__(BLOCK) void k_ply_rand(uint64_t* __restrict__ board
 }
 
 // OthelloEnv.step (othello.py:176-200) on one-word boards against a random or
-// greedy opponent: k_step_vs's control flow (device.hpp: the opponent's replies
+// greedy opponent: k_step_vs's control flow (vs.hpp: the opponent's replies
 // before and after the protagonist's ply, random-opening plies, the reward
 // negated after opponent plies, the W/D/L tallies, the auto-reset with the
 // opponent's opening reply) with every ply through step1 (computed rays,
@@ -555,16 +546,10 @@ __global__ __launch_bounds__(BLOCK) void k_step_vs1(uint64_t* __restrict__ board
                 pd_n = win == NO_DISK;
                 pl_n = win == -pcol;
                 if (flags & OTH_AUTO_RESET) {  // reset_vs_lane: reset, then the opponent's opening reply
-                    B = Start<N>::BLACK.w[0];
-                    Wt = Start<N>::WHITE.w[0];
-                    constexpr uint64_t START_MOVES = start_moves<N>();
-                    L = START_MOVES;
-                    uint32_t rl = 0;
-                    if (rng.init_rand > 0)
-                        rl = (uint32_t)scale_index(opening_draw(rng.seed, id, call, RNG_OPENING_AUTO),
-                                                   rng.init_rand / 2 + 1) * 2u;
-                    m = (rl & 0xffu) << M_RAND_SHIFT;
-                    if constexpr (KEEP) {  // the start position's fills (black to move)
+                    start_position<N>(B, Wt, L);
+                    m = reset_meta(rng.seed, id, call, RNG_OPENING_AUTO, rng.init_rand);
+                    if constexpr (KEEP) {  // the start position's fills (black to move); written out:
+                        // through start_position_fills this kernel's code comes out differently
                         constexpr StartFills<N> SF = start_fills<N>();
 #pragma unroll
                         for (int k = 0; k < 8; ++k) t[k] = SF.t[k];
@@ -593,12 +578,12 @@ __global__ __launch_bounds__(BLOCK) void k_step_vs1(uint64_t* __restrict__ board
     obs_tail<N, 64, 1>(obs_layout, obs_dtype, obs, e0, ob, ow, ol, m, (int)(E - e0 < 64 ? E - e0 : 64));
 }
 
-// oth_create: the handle's tables in device memory: the ray table (fill_rays<N,
-// true>'s 8 x 64 words) and the sel8 table (256 words, sel8_word) after it
+// oth_create: the handle's tables in device memory (tables.hpp): the four up
+// directions' rays and the sel8 table (sel8_word) after them
 template <int N>
-__global__ __launch_bounds__(BLOCK) void k_fill_rays(uint64_t* __restrict__ rays) {
-    fill_rays<N, true, false>(rays);
-    for (int i = threadIdx.x; i < 256; i += BLOCK) rays[8 * 64 + i] = sel8_word((uint32_t)i);
+__global__ __launch_bounds__(BLOCK) void k_fill_rays(uint64_t* __restrict__ tables) {
+    fill_rays<N, UP_RAY_WORDS / 64>(tables);
+    for (int i = threadIdx.x; i < SEL8_WORDS; i += BLOCK) tables[SEL8_AT + i] = sel8_word((uint32_t)i);
 }
 
 }  // namespace oth_dev

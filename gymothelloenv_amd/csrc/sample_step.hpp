@@ -4,7 +4,7 @@
 // layout uses.
 #pragma once
 
-#include "device.hpp"
+#include "masked.hpp"
 #include "ply.hpp"
 
 // (the observation tail at the end of the three kernels costs nothing when unused:
@@ -83,9 +83,7 @@ __global__ __launch_bounds__(BLOCK) void k_sample_step(uint64_t* __restrict__ bo
         int r, d, win;
         step_lane<N>(s, mine.a, flags, r, d, win, Solo<N>(0, nullptr));
         if (d && !was_term) {
-            cb = win == BLACK_DISK;
-            cd = win == NO_DISK;
-            cw = win == WHITE_DISK;
+            count_winner(win, cb, cd, cw);
             if (flags & OTH_AUTO_RESET)
                 reset_lane<N>(s, rng.seed, rng.id_base + (uint32_t)e, ply, RNG_OPENING_AUTO, rng.init_rand);
         }
@@ -161,11 +159,7 @@ __global__ __launch_bounds__(BLOCK) void k_sample_step2(uint64_t* __restrict__ b
             step_lane<N>(s, pk.a, flags, r, d, win, Solo<N>(0, nullptr));
         }
         if (d && !was_term) {
-            if (h == 0) {
-                cb = win == BLACK_DISK;
-                cd = win == NO_DISK;
-                cw = win == WHITE_DISK;
-            }
+            if (h == 0) count_winner(win, cb, cd, cw);
             if (flags & OTH_AUTO_RESET)
                 reset_lane<N>(s, rng.seed, rng.id_base + (uint32_t)e, ply, RNG_OPENING_AUTO, rng.init_rand);
         }
@@ -231,7 +225,7 @@ __global__ __launch_bounds__(BLOCK) void k_sample_step4(uint64_t* __restrict__ b
         load_lane<N>(s, boards, meta, legal, e);
         oth_ms::load_slot<1, 4, VEC>(b, q, NN, logits, ld, legal);
     }
-    fill_rays<N, false>(lds_rays);
+    fill_rays<N>(lds_rays);
     if (e < E) {  // quad-uniform: the four lanes of a quad share e
         const oth_ms::Pick pk = oth_ms::finish_slot<1, 4, FULL>(b, q, NN, logits, ld, uniforms, rng.seed, rng.id_base,
                                                                 counter, mode, 0, log_probs != nullptr,
@@ -240,7 +234,7 @@ __global__ __launch_bounds__(BLOCK) void k_sample_step4(uint64_t* __restrict__ b
         int r, d, win;
         step_lane<N>(s, pk.a, flags, r, d, win, eng);
         if (d && !was_term) {
-            if (q == 0) {
+            if (q == 0) {  // (written out: through count_winner the stores of the 4x4 .. 6x6 kernels move)
                 cb = win == BLACK_DISK;
                 cd = win == NO_DISK;
                 cw = win == WHITE_DISK;

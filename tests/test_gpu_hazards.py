@@ -19,35 +19,48 @@ from test_gpu_parity import flags_of, get_state_np, make_env, t64, torch_cuda  #
 pytestmark = pytest.mark.gpu
 
 
-def _load_live_empty(torch, env, n, stride):
-    """Mid-game state with every `stride`-th board's legal mask zeroed (still live)."""
+def _load_live_empty(torch, env, n, stride, terminated=()):
+    """Mid-game state with every `stride`-th board's legal mask zeroed (still live)
+    and the boards `terminated` marked as already terminated."""
     b, m, lg = get_state_np(env)
     lg = lg.copy()
     lg[::stride] = 0
     m = m.copy()
     m[::stride] &= ~np.uint16(2)  # live
+    m[list(terminated)] |= np.uint16(2)
     env.set_state(t64(torch, b), torch.from_numpy(m.view(np.int16)).cuda(), t64(torch, lg))
     return b, m, lg
 
 
-@pytest.mark.parametrize("n", [6, 8, 10])
+@pytest.mark.parametrize("n,init_rand", [(6, 0), (8, 0), (10, 0), (12, 0), (6, 4), (8, 4), (10, 4), (12, 4)],
+                         ids=["6", "8", "10", "12", "6-open4", "8-open4", "10-open4", "12-open4"])
 @pytest.mark.parametrize("policy", ["random", "greedy"])
-def test_live_boards_without_moves_take_the_invalid_path(torch_cuda, n, policy):
+def test_live_boards_without_moves_take_the_invalid_path(torch_cuda, n, init_rand, policy):
     """step_policy with auto-reset and every output recorded (the fast kernels'
     configuration) on waves holding live boards whose possible_moves is empty:
     action -1, the invalid path (sudden death here), no overlapping colours;
-    every action, reward, done, the final state and W/D/L equal the oracle."""
+    every action, reward, done, the final state and W/D/L equal the oracle.
+    12x12 (the three-word k_play_rand_w) and the cases with random openings also
+    load a few boards as already terminated, next to a live board without moves:
+    the generic loop then holds terminated boards, opening plies (every reset
+    draws 0, 2 or 4 of them) and boards in play in one wave, while the waves
+    without a doctored board run the fast loop in the same launch."""
     torch = torch_cuda
     E, plies, stride = 4096, 40, 300
-    env = make_env(torch, E, n, auto=True, seed=17)
+    terminated = [] if (n <= 10 and init_rand == 0) else list(range(stride + 1, E, 3 * stride))
+    doctored_waves = {e // 64 for e in list(range(0, E, stride)) + terminated}
+    assert all((e - 1) // 64 in doctored_waves for e in terminated) and len(doctored_waves) < E // 64
+    env = make_env(torch, E, n, auto=True, seed=17, init_rand=init_rand)
     env.step_policy("random", n_plies=9)
-    b, m, lg = _load_live_empty(torch, env, n, stride)
+    b, m, lg = _load_live_empty(torch, env, n, stride, terminated)
     env.counts(reset=True)
     acts, rews, dones = env.step_policy(policy, n_plies=plies)
     s = oracle.State(n, E)
     s.boards[:], s.meta[:], s.legal[:] = b, m, lg
     pid = 0 if policy == "random" else 1
-    oa, orw, od, owdl = oracle.rollout(s, flags_of(True, False, True), pid, plies, seed=17, ply0=9)
+    oa, orw, od, owdl = oracle.rollout(s, flags_of(True, False, True), pid, plies, seed=17, ply0=9,
+                                       initial_rand_steps=init_rand)
+    assert (oa[:, terminated] == -1).all() and (od[:, terminated] == 1).all()  # loaded terminated: they stay so
     acts = acts.cpu().numpy()
     np.testing.assert_array_equal(acts, oa)
     np.testing.assert_array_equal(rews.cpu().numpy(), orw)

@@ -2,7 +2,7 @@
 with random openings runs its plies in groups of four from a multiple of 4, with
 a partial group at either end of a launch; multi-word random play has a loop
 with the opening bookkeeping and one without.  Launches of odd lengths must give
-the plies one launch gives, and the oracle's replay (device.hpp k_play_rand,
+the plies one launch gives, and the oracle's replay (play.hpp k_play_rand,
 k_play_rand_w; the Philox draw of ply g is word g % 4 of block g / 4)."""
 import numpy as np
 import pytest
