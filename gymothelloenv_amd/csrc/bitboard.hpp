@@ -1186,34 +1186,73 @@ OTH_HD int select64(uint64_t x, int k) {
     return (up ? 32 : 0) + 8 * b + (un ? 4 : 0) + bit;
 }
 // The same select with the bit inside the byte read from a table (sel8: the
-// set-bit positions of every byte value, ascending, one byte each -- 2 KiB in
-// LDS, sel8_word): one ds_read_u8 in place of the nibble step's ~18 VALU.
+// set-bit positions of every byte value, one byte each -- 2 KiB in LDS,
+// sel8_word): one ds_read_u8 in place of the nibble step's ~18 VALU.  The j-th
+// set bit's position stands at byte 7 - j of its word, so that select64_tab's
+// e_b = -(j + 1) indexes it as it is, the 8 in the read's offset field.
 OTH_HD constexpr uint64_t sel8_word(uint32_t v) {
     uint64_t w = 0;
     int j = 0;
     for (int b = 0; b < 8; ++b)
         if ((v >> b) & 1u) {
-            w |= (uint64_t)b << (8 * j);
+            w |= (uint64_t)b << (8 * (7 - j));
             ++j;
         }
     return w;
 }
+// Without a compare or a select (a lone wave pays a v_cmp / v_cndmask pair more
+// than its two issue slots): the half by the sign mask of
+// k - c; then e_i = q_i - kk - 1 for the byte-prefix counts q_0 = 0 <= q_1 <= q_2
+// <= q_3, negative exactly where q_i <= kk.  The e_i grow with i, so as unsigned
+// numbers their maximum is the last negative one, e_b = q_b - kk - 1 = -(rank
+// inside byte b) - 1, and 8 b is the number of set bits in the e_i's top bytes.
+OTH_HD uint32_t sign_mask(int x) {  // all ones if x < 0
+#if defined(__HIP_DEVICE_COMPILE__)
+    int r;  // (as x >> 31 the backend makes a compare and a select of it again)
+    asm("v_ashrrev_i32 %0, 31, %1" : "=v"(r) : "v"(x));
+    return (uint32_t)r;
+#else
+    return x < 0 ? ~0u : 0u;
+#endif
+}
+OTH_HD uint32_t mask_pick(uint32_t m, uint32_t a, uint32_t b) {  // (m & a) | (~m & b)
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_bitop3_b32(m, a, b, 0xCA);
+#else
+    return (m & a) | (~m & b);
+#endif
+}
+// 8 * (how many of a, b, c are negative), each in [-2^23, 2^23): the top bytes
+// (0x00 or 0xFF) gathered by two v_perm_b32 and counted
+OTH_HD uint32_t negatives8(uint32_t a, uint32_t b, uint32_t c) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    const uint32_t ab = __builtin_amdgcn_perm(a, b, 0x0c0c0307u);  // {a[31:24], b[31:24], 0, 0}
+    return (uint32_t)__popc(__builtin_amdgcn_perm(ab, c, 0x0c030504u));
+#else
+    return 8u * ((a >> 31) + (b >> 31) + (c >> 31));
+#endif
+}
 OTH_HD int select64_tab(uint64_t x, int k, const uint8_t* sel8) {
     const uint32_t lo = (uint32_t)x;
-    const int c = popc64(lo);
-    const bool up = k >= c;
-    const uint32_t v = up ? (uint32_t)(x >> 32) : lo;
-    const int kk = up ? k - c : k;
-    const int q1 = popc64(v & 0xFFu), q2 = popc64(v & 0xFFFFu), q3 = popc64(v & 0xFFFFFFu);
-    const bool m1 = q1 <= kk, m2 = q2 <= kk, m3 = q3 <= kk;
-    const int b = (int)m1 + (int)m2 + (int)m3;
-    const int qb = m3 ? q3 : (m2 ? q2 : (m1 ? q1 : 0));
+    const int d = k - popc64(lo);
+    const uint32_t mu = sign_mask(d);  // the low half
+    const uint32_t v = mask_pick(mu, lo, (uint32_t)(x >> 32));
 #if defined(__HIP_DEVICE_COMPILE__)
-    const uint32_t byte = __builtin_amdgcn_ubfe(v, 8u * (uint32_t)b, 8u);  // v_bfe_u32
+    const uint32_t e0 = __builtin_amdgcn_bitop3_b32(mu, (uint32_t)k, (uint32_t)d, 0x35);  // ~mask_pick: -(kk + 1)
 #else
-    const uint32_t byte = (v >> (8 * b)) & 0xFFu;
+    const uint32_t e0 = ~mask_pick(mu, (uint32_t)k, (uint32_t)d);
 #endif
-    return (up ? 32 : 0) + 8 * b + sel8[8 * byte + (uint32_t)(kk - qb)];
+    const uint32_t e1 = (uint32_t)popc64(v & 0xFFu) + e0, e2 = (uint32_t)popc64(v & 0xFFFFu) + e0,
+                   e3 = (uint32_t)popc64(v & 0xFFFFFFu) + e0;
+    const uint32_t m12 = e1 > e2 ? e1 : e2, m03 = e0 > e3 ? e0 : e3;
+    const uint32_t eb = m12 > m03 ? m12 : m03;
+    const uint32_t b8 = negatives8(e1, e2, e3);
+#if defined(__HIP_DEVICE_COMPILE__)
+    const uint32_t byte = __builtin_amdgcn_ubfe(v, b8, 8u);  // v_bfe_u32
+#else
+    const uint32_t byte = (v >> b8) & 0xFFu;
+#endif
+    return (int)((~mu & 32u) + b8 + (sel8 + 8)[(int32_t)(8 * byte + eb)]);
 }
 // select_bit with select64_tab inside the word (k < popcount: a pick from a
 // non-empty mask), without branches: the word holding the k-th set bit picked by
