@@ -8,7 +8,7 @@ terminal/score) as HIP kernels for gfx950 behind a C ABI
     OthelloBaseEnv,          drop-in single-board classes with the
     SimpleOthelloEnv,        reference's constructor / attributes / 4-tuple step
     OthelloEnv
-    RandomPolicy, GreedyPolicy, MaxiMinPolicy, MonteCarloPolicy, make_state, undo_state
+    RandomPolicy, GreedyPolicy, MaxiMinPolicy, MonteCarloPolicy, SolverPolicy, make_state, undo_state
     masked_sample, masked_log_prob   policy-head sampling over legal squares
 """
 from ._lib import LIB_PATH, OthelloLibError, load  # noqa: F401
@@ -24,7 +24,7 @@ def __getattr__(name):
     if name in ("OthelloBaseEnv", "SimpleOthelloEnv", "OthelloEnv"):
         from . import othello
         return getattr(othello, name)
-    if name in ("RandomPolicy", "GreedyPolicy", "MaxiMinPolicy", "MonteCarloPolicy"):
+    if name in ("RandomPolicy", "GreedyPolicy", "MaxiMinPolicy", "MonteCarloPolicy", "SolverPolicy"):
         from . import policies
         return getattr(policies, name)
     if name in ("masked_sample", "masked_log_prob"):

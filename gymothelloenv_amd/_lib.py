@@ -37,6 +37,9 @@ OTH_MASKED_SAMPLE, OTH_MASKED_MODE, OTH_MASKED_EVAL = range(3)
 OTH_MASKED_FULL_ENTROPY = 4
 OTH_PLAYOUT_ROOT, OTH_PLAYOUT_MOVES = 0, 1  # oth_playouts modes
 OTH_PLAYOUTS_MAX = 65536
+OTH_SOLVE_MAX_EMPTIES = 14  # oth_solve
+OTH_SOLVE_NO_VALUE = -32768
+OTH_SOLVE_EXACT, OTH_SOLVE_TERMINATED, OTH_SOLVE_SKIPPED, OTH_SOLVE_NO_MOVE, OTH_SOLVE_ABORTED = range(5)
 OTH_GRAPH_SLOTS = 64
 OTH_GRAPH_COUNTER_SHIFT = 40
 
@@ -76,6 +79,7 @@ SIGNATURES = {
     "oth_step_sync": (_I32, [_P, _I32, _I32, _I32, _I32, ctypes.POINTER(_P), _P]),
     "oth_step_policy": (_I32, [_P, _I32, _I32, _P, _P, _P, _P]),
     "oth_playouts": (_I32, [_P, _I32, _I32, _U64, _U32, _U64, _P, _P, _P, _P]),
+    "oth_solve": (_I32, [_P, _I32, _U64, _P, _P, _P, _P, _P, _P]),
     "oth_reset_vs": (_I32, [_P, _I32, _P, _P, _P]),
     "oth_step_vs": (_I32, [_P, _I32, _P, _P, _P, _P, _P, _P]),
     "oth_step_vs_observe": (_I32, [_P, _I32, _P, _P, _P, _P, _P, _I32, _I32, _P, _P]),

@@ -406,6 +406,21 @@ int oth_playouts(oth_env* env, int32_t mode, int32_t n_playouts, uint64_t seed, 
     });
 }
 
+int oth_solve(oth_env* env, int32_t max_empties, uint64_t max_nodes, int32_t* value, int32_t* best,
+              int32_t* move_values, uint8_t* status, uint64_t* nodes, oth_stream_t stream) {
+    // the argument checks come before the handle is read
+    if (!env) return fail(OTH_EINVAL, "NULL oth_env");
+    if (!value) return fail(OTH_EINVAL, "value is NULL");
+    if (max_empties < 1 || max_empties > OTH_SOLVE_MAX_EMPTIES)
+        return fail(OTH_EINVAL, "max_empties must be in [1, 14]");
+    if (max_nodes < 1 || max_nodes > 0xffffffffull) return fail(OTH_EINVAL, "max_nodes must be in [1, 2^32 - 1]");
+    if (int rc = use_device(env)) return rc;
+    return with_n(env->n, [&](auto NC) {
+        return launch_solve<decltype(NC)::value>(env, max_empties, (uint32_t)max_nodes, value, best, move_values,
+                                                 status, nodes, (hipStream_t)stream);
+    });
+}
+
 int oth_reset_vs(oth_env* env, int32_t opponent_policy, const int8_t* protagonist, const uint8_t* mask,
                  oth_stream_t stream) {
     OTH_CHECK_ENV(env);

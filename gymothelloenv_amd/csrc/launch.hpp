@@ -115,4 +115,9 @@ template <int N>
 int launch_playouts(oth_env* env, int mode, int n_playouts, uint64_t seed, uint32_t id_key, uint64_t counter,
                     int32_t* wdl, int32_t* score, int32_t* best, hipStream_t st);
 
+// k_solve (oth_solve) in solve_n.hip, every N, a unit of its own per board size
+template <int N>
+int launch_solve(oth_env* env, int max_empties, uint32_t max_nodes, int32_t* value, int32_t* best,
+                 int32_t* move_values, uint8_t* status, uint64_t* nodes, hipStream_t st);
+
 }  // namespace oth_host

@@ -152,4 +152,37 @@ class MonteCarloPolicy(object):
         return self.get_action(obs)
 
 
-__all__ = ['RandomPolicy', 'GreedyPolicy', 'MaxiMinPolicy', 'MonteCarloPolicy', 'PROTAGONIST_TURN', 'OPPONENT_TURN', 'WHITE_DISK']
+class SolverPolicy(object):
+    """Perfect endgame play (no reference counterpart): once the board has at most
+    max_empties empty squares the move is the exact solver's `best` (oth_solve: the
+    move of the largest final disc difference under best play by both sides, lowest
+    square on ties).  Wherever the solver gives no exact answer -- more empty
+    squares (SKIPPED), or a search over its node budget (ABORTED) -- `fallback`
+    moves instead: GreedyPolicy() by default, or any policy of this protocol."""
+
+    def __init__(self, max_empties=10, fallback=None):
+        self.env = None
+        self.max_empties = int(max_empties)
+        self.fallback = fallback if fallback is not None else GreedyPolicy()
+
+    def reset(self, env):
+        self.env = _base(env)
+        self.fallback.reset(env)
+
+    def seed(self, seed):
+        if hasattr(self.fallback, 'seed'):
+            self.fallback.seed(seed)
+
+    def get_action(self, obs):
+        vec = self.env._vec
+        self.env._sync()
+        best, status = vec.solve(max_empties=self.max_empties, best=True, status=True)[1:]
+        if int(status.cpu()[0]) == L.OTH_SOLVE_EXACT:
+            return int(best.cpu()[0])
+        return self.fallback.get_action(obs)
+
+    def get_test_action(self, obs):
+        return self.get_action(obs)
+
+
+__all__ = ['RandomPolicy', 'GreedyPolicy', 'MaxiMinPolicy', 'MonteCarloPolicy', 'SolverPolicy', 'PROTAGONIST_TURN', 'OPPONENT_TURN', 'WHITE_DISK']

@@ -465,6 +465,44 @@ class VecOthelloEnv(object):
     def playout_counter(self, v):
         self._playout_calls = int(v)
 
+    # ------------------------------------------------------------ exact endgame
+    def solve(self, max_empties=10, max_nodes=1 << 22, best=False, move_values=False, status=False, nodes=False):
+        """Exact endgame values (oth_solve): for every live board with at most
+        max_empties (<= 14) empty squares, the final disc difference under best
+        play by both sides, from the side to move; the boards, the ply counter and
+        the tallies are left untouched, and no random number is drawn.
+
+        Returns value, then best, move_values, status and nodes when asked (the
+        header's order), as tensors on this device:
+          value       int32 (E,); OTH_SOLVE_NO_VALUE (-32768) where there is none;
+          best        int32 (E,): the lowest possible move that attains value, -1 without;
+          move_values int32 (E, N*N): the value of every stored possible move;
+          status      uint8 (E,): OTH_SOLVE_EXACT / TERMINATED / SKIPPED (more than
+                      max_empties empty squares: no search) / NO_MOVE / ABORTED;
+          nodes       int64 (E,) (the C ABI's uint64): disc placements searched.
+        max_nodes bounds the search of one root move (status ABORTED beyond it).
+        Its default started as a guess; tools/probe_solve.py then found no board
+        over it among 65,536 random-play 8x8 positions with 10 empty squares (the
+        largest board searched 9.0e5 nodes over all its moves) nor among 1,024 with
+        12, so it stayed.  Other board sizes are unmeasured."""
+        E, nn = self.num_envs, self.board_size * self.board_size
+        val = self._i32(E)
+        bt = self._i32(E) if best else None
+        mv = self._i32(E, nn) if move_values else None
+        stt = self._u8(E) if status else None
+        nd = torch.empty(E, dtype=torch.int64, device=self.device) if nodes else None
+        L.check(self._lib.oth_solve(self._h, int(max_empties), int(max_nodes), _ptr(val), _ptr(bt), _ptr(mv),
+                                    _ptr(stt), _ptr(nd), self._stream()), "oth_solve")
+        res = (val,) + tuple(t for t in (bt, mv, stt, nd) if t is not None)
+        return res[0] if len(res) == 1 else res
+
+    def solve_actions(self, **kw):
+        """Every board's exactly best move (solve(best=True)'s `best`): int32 (E,),
+        -1 where the solver gives none (see solve's status)."""
+        for k in ("best", "move_values", "status", "nodes"):
+            kw.pop(k, None)
+        return self.solve(best=True, **kw)[1]
+
     def _sampler_inputs(self, logits, uniforms):
         """(logits rows, uniforms) checked before a launch reads them: the rows on
         this handle's device, one per board; uniforms float32 on it, >= E of them."""

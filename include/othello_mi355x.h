@@ -215,6 +215,68 @@ enum { OTH_PLAYOUT_ROOT = 0, OTH_PLAYOUT_MOVES = 1 };
 int oth_playouts(oth_env *env, int32_t mode, int32_t n_playouts /* R */, uint64_t seed, uint32_t id_key,
                  uint64_t counter, int32_t *wdl, int32_t *score, int32_t *best, oth_stream_t stream);
 
+/* Exact endgame values and best moves of the handle's live positions (no
+ * reference counterpart: what a position is worth, where playouts estimate).
+ *
+ * The value.  G(pos, mover) is the final disc difference under best play by
+ * both sides, counted from mover's side, with the reference's end-of-game
+ * rules (othello.py:424-442, 473-501):
+ *   game end (the board is full, or neither side has a move):
+ *       G = discs(mover) - discs(other): raw counts, no bonus for empty
+ *       squares, the quantity oth_playouts sums in `score`; sign(G) is
+ *       determine_winner from the mover's side;
+ *   the mover has moves:  G = max over moves a of -G(pos after a, other);
+ *   the mover has no move but the other side has (a pass):
+ *       G = -G(pos, other); no disc is placed.
+ * At the root the move list is the handle's stored possible_moves[e], as
+ * oth_step and oth_playouts (MOVES) treat it: after oth_set_state with a
+ * narrower mask only those squares are valued.  Each root move is oth_step's
+ * ply with flags 0; below the root, moves are recomputed from the boards.
+ *
+ * Handle state.  The call writes nothing of the handle: boards, meta,
+ * possible_moves, the ply counter, the graph offsets and both tallies stay as
+ * they are.  It only enqueues work, never synchronises the host, is capturable
+ * into a HIP graph and draws no random number.
+ *
+ * Outputs (device pointers; every element of every non-NULL output is written,
+ * nothing needs zeroing): value int32[E] (required); best int32[E],
+ * move_values int32[E][N*N], status uint8[E], nodes uint64[E] (each may be
+ * NULL).  By status:
+ *   TERMINATED  meta bit 1 set.  value = discs(side in the turn bit) -
+ *               discs(other); best -1; move_values all OTH_SOLVE_NO_VALUE.
+ *   SKIPPED     live, more than max_empties empty squares (N*N -
+ *               popcount(black | white)).  value OTH_SOLVE_NO_VALUE, best -1,
+ *               move_values all NO_VALUE.  No search work is launched for it.
+ *   NO_MOVE     live, stored possible_moves empty: as SKIPPED.
+ *   EXACT       otherwise.  move_values[a] = -G(after a, other) for every
+ *               stored possible move a, NO_VALUE elsewhere; value their
+ *               maximum; best the lowest square that attains it.
+ *   ABORTED     some root move's search visited more than max_nodes nodes.
+ *               value NO_VALUE, best -1; move_values exact for the moves that
+ *               finished, NO_VALUE for the abandoned ones.
+ * Nodes.  A node is a position reached by placing a disc: the root's children
+ * count, a pass adds none.  nodes[e] is the sum over the board's root moves (an
+ * abandoned move adds max_nodes + 1); 0 for every status but EXACT and ABORTED.
+ * The budget max_nodes, in [1, 2^32 - 1], is per root move and bounds the
+ * kernel's running time whatever the input.
+ *
+ * Determinism.  value, best, move_values, status and nodes of a board are
+ * functions of that board's state and the two limits alone: not of E, the
+ * board's index, its neighbours or how tasks are mapped to lanes (one lane
+ * searches one root move with the full window; no bound is shared).  Two
+ * calls give identical bytes.
+ *
+ * OTH_EINVAL: NULL handle, NULL value, max_empties outside [1,
+ * OTH_SOLVE_MAX_EMPTIES], max_nodes outside its range; checked before the
+ * handle is read.  Every board size works. */
+#define OTH_SOLVE_MAX_EMPTIES 14
+#define OTH_SOLVE_NO_VALUE (-32768)
+enum { OTH_SOLVE_EXACT = 0, OTH_SOLVE_TERMINATED = 1, OTH_SOLVE_SKIPPED = 2,
+       OTH_SOLVE_NO_MOVE = 3, OTH_SOLVE_ABORTED = 4 };
+int oth_solve(oth_env *env, int32_t max_empties, uint64_t max_nodes,
+              int32_t *value, int32_t *best, int32_t *move_values,
+              uint8_t *status, uint64_t *nodes, oth_stream_t stream);
+
 /* OthelloEnv (othello.py:96-214) for every env: the protagonist's colour per
  * env (protagonist: device int8[E] of +1 white / -1 black, NULL = all white,
  * the reference default) and an embedded opponent played on the device
