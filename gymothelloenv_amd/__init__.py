@@ -8,7 +8,9 @@ terminal/score) as HIP kernels for gfx950 behind a C ABI
     OthelloBaseEnv,          drop-in single-board classes with the
     SimpleOthelloEnv,        reference's constructor / attributes / 4-tuple step
     OthelloEnv
-    RandomPolicy, GreedyPolicy, MaxiMinPolicy, MonteCarloPolicy, SolverPolicy, make_state, undo_state
+    RandomPolicy, GreedyPolicy, MaxiMinPolicy, MonteCarloPolicy, SolverPolicy, SearchPolicy,
+    make_state, undo_state
+    default_search_weights   the conventional square weights of VecOthelloEnv.search
     masked_sample, masked_log_prob   policy-head sampling over legal squares
 """
 from ._lib import LIB_PATH, OthelloLibError, load  # noqa: F401
@@ -18,13 +20,14 @@ BLACK_DISK, NO_DISK, WHITE_DISK = -1, 0, 1
 
 def __getattr__(name):
     # lazy: importing the package must not touch the GPU (build() runs on CPU hosts)
-    if name in ("VecOthelloEnv", "legal_moves"):
+    if name in ("VecOthelloEnv", "legal_moves", "default_search_weights"):
         from . import vec_env
         return getattr(vec_env, name)
     if name in ("OthelloBaseEnv", "SimpleOthelloEnv", "OthelloEnv"):
         from . import othello
         return getattr(othello, name)
-    if name in ("RandomPolicy", "GreedyPolicy", "MaxiMinPolicy", "MonteCarloPolicy", "SolverPolicy"):
+    if name in ("RandomPolicy", "GreedyPolicy", "MaxiMinPolicy", "MonteCarloPolicy", "SolverPolicy",
+                "SearchPolicy"):
         from . import policies
         return getattr(policies, name)
     if name in ("masked_sample", "masked_log_prob"):

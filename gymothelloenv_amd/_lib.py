@@ -40,6 +40,9 @@ OTH_PLAYOUTS_MAX = 65536
 OTH_SOLVE_MAX_EMPTIES = 14  # oth_solve
 OTH_SOLVE_NO_VALUE = -32768
 OTH_SOLVE_EXACT, OTH_SOLVE_TERMINATED, OTH_SOLVE_SKIPPED, OTH_SOLVE_NO_MOVE, OTH_SOLVE_ABORTED = range(5)
+OTH_SEARCH_MAX_DEPTH = 14  # oth_search
+OTH_SEARCH_NO_VALUE = -2 ** 31
+OTH_SEARCH_DONE, OTH_SEARCH_TERMINATED, OTH_SEARCH_NO_MOVE, OTH_SEARCH_ABORTED = 0, 1, 3, 4
 OTH_GRAPH_SLOTS = 64
 OTH_GRAPH_COUNTER_SHIFT = 40
 
@@ -80,6 +83,7 @@ SIGNATURES = {
     "oth_step_policy": (_I32, [_P, _I32, _I32, _P, _P, _P, _P]),
     "oth_playouts": (_I32, [_P, _I32, _I32, _U64, _U32, _U64, _P, _P, _P, _P]),
     "oth_solve": (_I32, [_P, _I32, _U64, _P, _P, _P, _P, _P, _P]),
+    "oth_search": (_I32, [_P, _I32, _P, _I32, _I32, _U64, _P, _P, _P, _P, _P, _P]),
     "oth_reset_vs": (_I32, [_P, _I32, _P, _P, _P]),
     "oth_step_vs": (_I32, [_P, _I32, _P, _P, _P, _P, _P, _P]),
     "oth_step_vs_observe": (_I32, [_P, _I32, _P, _P, _P, _P, _P, _I32, _I32, _P, _P]),

@@ -421,6 +421,27 @@ int oth_solve(oth_env* env, int32_t max_empties, uint64_t max_nodes, int32_t* va
     });
 }
 
+int oth_search(oth_env* env, int32_t depth, const int8_t* weights, int32_t mobility_weight, int32_t terminal_weight,
+               uint64_t max_nodes, int32_t* value, int32_t* best, int32_t* move_values, uint8_t* status,
+               uint64_t* nodes, oth_stream_t stream) {
+    // the argument checks come before the handle is read
+    if (!env) return fail(OTH_EINVAL, "NULL oth_env");
+    if (!value) return fail(OTH_EINVAL, "value is NULL");
+    if (!weights) return fail(OTH_EINVAL, "weights is NULL");
+    if (depth < 1 || depth > OTH_SEARCH_MAX_DEPTH) return fail(OTH_EINVAL, "depth must be in [1, 14]");
+    if (mobility_weight < -127 || mobility_weight > 127)
+        return fail(OTH_EINVAL, "mobility_weight must be in [-127, 127]");
+    if (terminal_weight < 1 || terminal_weight > 32767)
+        return fail(OTH_EINVAL, "terminal_weight must be in [1, 32767]");
+    if (max_nodes < 1 || max_nodes > 0xffffffffull) return fail(OTH_EINVAL, "max_nodes must be in [1, 2^32 - 1]");
+    if (int rc = use_device(env)) return rc;
+    return with_n(env->n, [&](auto NC) {
+        return launch_search<decltype(NC)::value>(env, depth, weights, mobility_weight, terminal_weight,
+                                                  (uint32_t)max_nodes, value, best, move_values, status, nodes,
+                                                  (hipStream_t)stream);
+    });
+}
+
 int oth_reset_vs(oth_env* env, int32_t opponent_policy, const int8_t* protagonist, const uint8_t* mask,
                  oth_stream_t stream) {
     OTH_CHECK_ENV(env);

@@ -120,4 +120,10 @@ template <int N>
 int launch_solve(oth_env* env, int max_empties, uint32_t max_nodes, int32_t* value, int32_t* best,
                  int32_t* move_values, uint8_t* status, uint64_t* nodes, hipStream_t st);
 
+// k_search (oth_search) in search_n.hip, every N, a unit of its own per board size
+template <int N>
+int launch_search(oth_env* env, int depth, const int8_t* weights, int mobility, int terminal, uint32_t max_nodes,
+                  int32_t* value, int32_t* best, int32_t* move_values, uint8_t* status, uint64_t* nodes,
+                  hipStream_t st);
+
 }  // namespace oth_host

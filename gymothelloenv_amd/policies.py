@@ -185,4 +185,40 @@ class SolverPolicy(object):
         return self.get_action(obs)
 
 
-__all__ = ['RandomPolicy', 'GreedyPolicy', 'MaxiMinPolicy', 'MonteCarloPolicy', 'SolverPolicy', 'PROTAGONIST_TURN', 'OPPONENT_TURN', 'WHITE_DISK']
+class SearchPolicy(object):
+    """Depth-limited alpha-beta over weighted squares and mobility (no reference
+    counterpart: the fixed middle-game opponent): the move is oth_search's `best`
+    at `depth` with `weights` (None: default_search_weights), `mobility` and
+    `terminal` as VecOthelloEnv.search takes them.  With solve_empties > 0 a board
+    with at most that many empty squares goes to the exact solver first (oth_solve)
+    and the search moves where the solver does not answer EXACT.  Where the search
+    runs over its node budget (ABORTED) GreedyPolicy moves, as for SolverPolicy."""
+
+    def __init__(self, depth=4, weights=None, mobility=0, terminal=64, solve_empties=0):
+        self.env = None
+        self.depth, self.weights, self.mobility, self.terminal = int(depth), weights, int(mobility), int(terminal)
+        self.solve_empties = int(solve_empties)
+        self.fallback = GreedyPolicy()
+
+    def reset(self, env):
+        self.env = _base(env)
+        self.fallback.reset(env)
+
+    def get_action(self, obs):
+        vec = self.env._vec
+        self.env._sync()
+        if self.solve_empties > 0:
+            best, status = vec.solve(max_empties=self.solve_empties, best=True, status=True)[1:]
+            if int(status.cpu()[0]) == L.OTH_SOLVE_EXACT:
+                return int(best.cpu()[0])
+        best, status = vec.search(self.depth, self.weights, mobility=self.mobility, terminal=self.terminal,
+                                  best=True, status=True)[1:]
+        if int(status.cpu()[0]) == L.OTH_SEARCH_DONE:
+            return int(best.cpu()[0])
+        return self.fallback.get_action(obs)
+
+    def get_test_action(self, obs):
+        return self.get_action(obs)
+
+
+__all__ = ['RandomPolicy', 'GreedyPolicy', 'MaxiMinPolicy', 'MonteCarloPolicy', 'SolverPolicy', 'SearchPolicy', 'PROTAGONIST_TURN', 'OPPONENT_TURN', 'WHITE_DISK']

@@ -503,6 +503,66 @@ class VecOthelloEnv(object):
             kw.pop(k, None)
         return self.solve(best=True, **kw)[1]
 
+    # ------------------------------------------------------- depth-limited search
+    def _search_weights(self, weights):
+        """weights as the device int8 (N*N,) tensor oth_search reads."""
+        nn = self.board_size * self.board_size
+        if weights is None:  # moved to the device once: a captured call copies nothing
+            if getattr(self, "_default_w", None) is None:
+                self._default_w = default_search_weights(self.board_size).reshape(nn).to(self.device)
+            return self._default_w
+        w = torch.as_tensor(weights)
+        if w.is_floating_point() or w.is_complex() or w.dtype == torch.bool:
+            raise ValueError("weights must be integers")
+        if w.numel() != nn or w.dim() not in (1, 2) or (w.dim() == 2 and w.shape[0] != self.board_size):
+            raise ValueError("weights must have shape (N, N) or (N*N,)")
+        if w.dtype != torch.int8:
+            if int(w.min()) < -128 or int(w.max()) > 127:
+                raise ValueError("weights must fit int8")
+            w = w.to(torch.int8)
+        return w.reshape(nn).to(self.device).contiguous()
+
+    def search(self, depth, weights=None, mobility=0, terminal=64, max_nodes=1 << 22, best=False, move_values=False,
+               status=False, nodes=False):
+        """Depth-limited alpha-beta (oth_search) of every live board, whatever its
+        number of empty squares: `depth` (1..14) discs ahead, the frontier valued by
+        weighted squares plus mobility,
+            sum_a weights[a] ([a mine] - [a theirs]) + mobility (my moves - their moves),
+        and a game end by terminal * (my discs - their discs), all from the side to
+        move; a pass consumes no depth.  weights: an (N, N) or (N*N,) integer tensor
+        or array that fits int8 (None: default_search_weights(N)); mobility in
+        [-127, 127]; terminal in [1, 32767].  The boards, the ply counter and the
+        tallies are left untouched, and no random number is drawn.
+
+        Returns value, then best, move_values, status and nodes when asked, as
+        solve() does: value int32 (E,) with OTH_SEARCH_NO_VALUE (-2^31) where there
+        is none; status OTH_SEARCH_DONE / TERMINATED / NO_MOVE / ABORTED (more than
+        max_nodes disc placements under one root move).  max_nodes' default
+        started as a guess; tools/probe_search.py then found no board over it at
+        depths 1-5 among 65,536 random-play 8x8 positions with 30 empty squares nor
+        with 20 (the largest board searched 5.3e5 nodes over all its moves at depth
+        5), so it stayed.  Deeper searches and other board
+        sizes are unmeasured."""
+        E, nn = self.num_envs, self.board_size * self.board_size
+        w = self._search_weights(weights)
+        val = self._i32(E)
+        bt = self._i32(E) if best else None
+        mv = self._i32(E, nn) if move_values else None
+        stt = self._u8(E) if status else None
+        nd = torch.empty(E, dtype=torch.int64, device=self.device) if nodes else None
+        L.check(self._lib.oth_search(self._h, int(depth), _ptr(w), int(mobility), int(terminal), int(max_nodes),
+                                     _ptr(val), _ptr(bt), _ptr(mv), _ptr(stt), _ptr(nd), self._stream()),
+                "oth_search")
+        res = (val,) + tuple(t for t in (bt, mv, stt, nd) if t is not None)
+        return res[0] if len(res) == 1 else res
+
+    def search_actions(self, **kw):
+        """Every board's best move of the search (search(best=True)'s `best`): int32
+        (E,), -1 where the search gives none (see search's status)."""
+        for k in ("best", "move_values", "status", "nodes"):
+            kw.pop(k, None)
+        return self.search(best=True, **kw)[1]
+
     def _sampler_inputs(self, logits, uniforms):
         """(logits rows, uniforms) checked before a launch reads them: the rows on
         this handle's device, one per board; uniforms float32 on it, >= E of them."""
@@ -698,6 +758,29 @@ def _numel(shape):
 def _no_capture(what):
     if torch.cuda.is_current_stream_capturing():
         raise RuntimeError("%s synchronises the device and cannot run during a HIP-graph capture" % what)
+
+
+def default_search_weights(n):
+    """The square weights VecOthelloEnv.search uses when it is given none: an int8
+    (n, n) tensor on the host, by square class -- corner 100, X-square (a corner's
+    diagonal neighbour) -50, C-square (a corner's orthogonal neighbour) -20, any
+    other edge square 10, the rest 0; where the classes overlap on small boards
+    the precedence is corner > X > C > edge.  A conventional shape, not a tuned
+    table: its playing strength is unmeasured."""
+    n = int(n)
+    w = torch.zeros(n, n, dtype=torch.int8)
+    w[0, :] = w[-1, :] = 10
+    w[:, 0] = w[:, -1] = 10
+    for r, dr in ((0, 1), (n - 1, -1)):
+        for c, dc in ((0, 1), (n - 1, -1)):
+            w[r + dr, c] = w[r, c + dc] = -20
+    for r, dr in ((0, 1), (n - 1, -1)):
+        for c, dc in ((0, 1), (n - 1, -1)):
+            w[r + dr, c + dc] = -50
+    for r in (0, n - 1):
+        for c in (0, n - 1):
+            w[r, c] = 100
+    return w
 
 
 def legal_moves(board_size, mover, opponent):

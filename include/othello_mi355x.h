@@ -277,6 +277,69 @@ int oth_solve(oth_env *env, int32_t max_empties, uint64_t max_nodes,
               int32_t *value, int32_t *best, int32_t *move_values,
               uint8_t *status, uint64_t *nodes, oth_stream_t stream);
 
+/* Depth-limited alpha-beta over a positional evaluation the caller supplies
+ * (no reference counterpart: the middle game's deterministic look-ahead, where
+ * oth_solve serves the last 14 empty squares; the evaluation is the "weighted
+ * piece counter" plus mobility).
+ *
+ * The value.  M: the discs of the side to move, O: the other side's, L(M, O):
+ * get_possible_actions for M against O.
+ *   evaluation  H(M, O) = sum_a weights[a] ([a in M] - [a in O])
+ *                         + mobility_weight (|L(M, O)| - |L(O, M)|)
+ *   game end    T(M, O) = terminal_weight (|M| - |O|): raw disc counts, as oth_solve's
+ * V_d(M, O), with d discs still to place, is the first rule that applies:
+ *   1. game end (the board is full, or L(M, O) and L(O, M) are both empty): T(M, O);
+ *   2. d == 0: H(M, O) -- also for a mover without a move: the mobility term
+ *      sees it, no pass is played at the frontier;
+ *   3. the mover has no move and the other side has one: -V_d(O, M); a pass
+ *      places no disc and consumes no depth;
+ *   4. otherwise max over a in L(M, O) of -V_{d-1}(position after a, other side).
+ * At the root the move list is the handle's stored possible_moves[e] (as
+ * oth_step, oth_playouts in MOVES mode and oth_solve treat it), each root move
+ * is oth_step's ply with flags 0, move_values[a] = -V_{depth-1}(after a),
+ * value is their maximum and best the lowest square that attains it.
+ *
+ * Ranges: depth in [1, OTH_SEARCH_MAX_DEPTH]; weights device int8[N*N], any
+ * value, -128 included; mobility_weight in [-127, 127]; terminal_weight in
+ * [1, 32767]; max_nodes in [1, 2^32 - 1], per root move.  Then |H| <= 128 * 256
+ * + 127 * 256 < 2^16 and |T| <= 32767 * 256 < 2^23: every value lies strictly
+ * inside (-2^24, 2^24), the bound the kernel's frames and reduction keys rely
+ * on.  With depth beyond the end of the game and terminal_weight 1 the values
+ * are oth_solve's.
+ *
+ * Outputs, nodes, determinism and handle state are oth_solve's contract (every
+ * element of every non-NULL output is written; value is required, the others
+ * may be NULL), with the status codes' numbers kept; code 2 (SKIPPED) never
+ * occurs, any number of empty squares is searched:
+ *   TERMINATED  value = terminal_weight (discs(side in the turn bit) -
+ *               discs(other)); best -1; move_values all OTH_SEARCH_NO_VALUE.
+ *   NO_MOVE     live, stored possible_moves empty: value NO_VALUE, best -1,
+ *               move_values all NO_VALUE.
+ *   DONE        move_values[a] for every stored possible move a, NO_VALUE
+ *               elsewhere; value and best as above.
+ *   ABORTED     some root move's search placed more than max_nodes discs:
+ *               value NO_VALUE, best -1; the finished moves keep their values,
+ *               the abandoned ones get NO_VALUE.
+ * A node is a position reached by placing a disc; nodes[e] sums the board's
+ * root moves (an abandoned move adds max_nodes + 1), 0 for TERMINATED and
+ * NO_MOVE.  The search is the solver's fail-soft negamax: moves in ascending
+ * squares, a node finished when best >= beta, the child's window
+ * (-beta, -max(alpha, best)), a pass in place with the window negated, each
+ * root move a pseudo-node with the full window.  So every output, nodes
+ * included, is a function of the board, the weights and the limits alone, not
+ * of E, the board's index or the lane mapping; two calls give identical bytes.
+ * The call writes nothing of the handle, draws no random number, only enqueues
+ * work and is capturable into a HIP graph.
+ *
+ * OTH_EINVAL: NULL handle, NULL value, NULL weights, a limit out of range;
+ * checked before the handle is read.  Every board size works. */
+#define OTH_SEARCH_MAX_DEPTH 14
+#define OTH_SEARCH_NO_VALUE INT32_MIN
+enum { OTH_SEARCH_DONE = 0, OTH_SEARCH_TERMINATED = 1, OTH_SEARCH_NO_MOVE = 3, OTH_SEARCH_ABORTED = 4 };
+int oth_search(oth_env *env, int32_t depth, const int8_t *weights, int32_t mobility_weight,
+               int32_t terminal_weight, uint64_t max_nodes, int32_t *value, int32_t *best,
+               int32_t *move_values, uint8_t *status, uint64_t *nodes, oth_stream_t stream);
+
 /* OthelloEnv (othello.py:96-214) for every env: the protagonist's colour per
  * env (protagonist: device int8[E] of +1 white / -1 black, NULL = all white,
  * the reference default) and an embedded opponent played on the device
