@@ -11,6 +11,8 @@ terminal/score) as HIP kernels for gfx950 behind a C ABI
     RandomPolicy, GreedyPolicy, MaxiMinPolicy, MonteCarloPolicy, SolverPolicy, SearchPolicy,
     make_state, undo_state
     default_search_weights   the conventional square weights of VecOthelloEnv.search
+    SearchConfig             a search as a player: VecOthelloEnv.play_search, and the
+                             opponent of reset_vs / step_vs
     masked_sample, masked_log_prob   policy-head sampling over legal squares
 """
 from ._lib import LIB_PATH, OthelloLibError, load  # noqa: F401
@@ -20,7 +22,7 @@ BLACK_DISK, NO_DISK, WHITE_DISK = -1, 0, 1
 
 def __getattr__(name):
     # lazy: importing the package must not touch the GPU (build() runs on CPU hosts)
-    if name in ("VecOthelloEnv", "legal_moves", "default_search_weights"):
+    if name in ("VecOthelloEnv", "legal_moves", "default_search_weights", "SearchConfig"):
         from . import vec_env
         return getattr(vec_env, name)
     if name in ("OthelloBaseEnv", "SimpleOthelloEnv", "OthelloEnv"):

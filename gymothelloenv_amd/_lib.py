@@ -70,6 +70,17 @@ class OthRecord(ctypes.Structure):
                 ("board_state", ctypes.c_int8 * OTH_RECORD_MAX_SQUARES)]
 
 
+class OthSearchPolicy(ctypes.Structure):
+    """struct oth_search_policy (include/othello_mi355x.h): one colour's search
+    configuration, host memory read during the call; `weights` is a device address."""
+    _fields_ = [("weights", ctypes.c_void_p),
+                ("depth", ctypes.c_int32),
+                ("mobility_weight", ctypes.c_int32),
+                ("terminal_weight", ctypes.c_int32),
+                ("endgame_empties", ctypes.c_int32),
+                ("max_nodes", ctypes.c_uint64)]
+
+
 # every symbol include/othello_mi355x.h declares: (restype, argtypes)
 _P = ctypes.c_void_p
 _I32, _U32, _U64, _I64 = ctypes.c_int32, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_int64
@@ -84,6 +95,9 @@ SIGNATURES = {
     "oth_playouts": (_I32, [_P, _I32, _I32, _U64, _U32, _U64, _P, _P, _P, _P]),
     "oth_solve": (_I32, [_P, _I32, _U64, _P, _P, _P, _P, _P, _P]),
     "oth_search": (_I32, [_P, _I32, _P, _I32, _I32, _U64, _P, _P, _P, _P, _P, _P]),
+    "oth_play_search": (_I32, [_P, _P, _P, _I32, _P, _P, _P, _P, _P]),
+    "oth_reset_vs_search": (_I32, [_P, _P, _P, _P, _P]),
+    "oth_step_vs_search": (_I32, [_P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "oth_reset_vs": (_I32, [_P, _I32, _P, _P, _P]),
     "oth_step_vs": (_I32, [_P, _I32, _P, _P, _P, _P, _P, _P]),
     "oth_step_vs_observe": (_I32, [_P, _I32, _P, _P, _P, _P, _P, _I32, _I32, _P, _P]),

@@ -442,6 +442,74 @@ int oth_search(oth_env* env, int32_t depth, const int8_t* weights, int32_t mobil
     });
 }
 
+}  // extern "C"
+
+namespace {
+// an oth_search_policy's ranges (oth_search's); who: the argument's name for the message
+int check_search_policy(const oth_search_policy* p, const char* who) {
+    char msg[160];
+    const char* why = nullptr;
+    if (!p) why = "is NULL";
+    else if (!p->weights) why = "has NULL weights";
+    else if (p->depth < 1 || p->depth > OTH_SEARCH_MAX_DEPTH) why = "depth must be in [1, 14]";
+    else if (p->mobility_weight < -127 || p->mobility_weight > 127) why = "mobility_weight must be in [-127, 127]";
+    else if (p->terminal_weight < 1 || p->terminal_weight > 32767) why = "terminal_weight must be in [1, 32767]";
+    else if (p->endgame_empties < 0 || p->endgame_empties > OTH_SEARCH_MAX_DEPTH)
+        why = "endgame_empties must be in [0, 14]";
+    else if (p->max_nodes < 1 || p->max_nodes > 0xffffffffull) why = "max_nodes must be in [1, 2^32 - 1]";
+    if (!why) return OTH_OK;
+    snprintf(msg, sizeof(msg), "search policy `%s`: %s", who, why);
+    return fail(OTH_EINVAL, msg);
+}
+}  // namespace
+
+extern "C" {
+
+int oth_play_search(oth_env* env, const oth_search_policy* black, const oth_search_policy* white, int32_t n_plies,
+                    int32_t* actions, int32_t* rewards, uint8_t* dones, uint8_t* fallbacks, oth_stream_t stream) {
+    // the argument checks come before the handle is read
+    if (!env) return fail(OTH_EINVAL, "NULL oth_env");
+    if (int rc = check_search_policy(black, "black")) return rc;
+    if (int rc = check_search_policy(white, "white")) return rc;
+    if (n_plies < 1) return fail(OTH_EINVAL, "n_plies must be >= 1");
+    if (int rc = use_device(env)) return rc;
+    const uint64_t ply0 = env->ply;
+    env->ply += (uint64_t)n_plies;
+    return with_n(env->n, [&](auto NC) {
+        return launch_play_search<decltype(NC)::value>(env, OTH_PLAY_SEARCH_PLAY, black, white, n_plies, nullptr,
+                                                       nullptr, nullptr, actions, rewards, dones, fallbacks, nullptr,
+                                                       nullptr, ply0, (hipStream_t)stream);
+    });
+}
+
+int oth_reset_vs_search(oth_env* env, const oth_search_policy* opponent, const int8_t* protagonist,
+                        const uint8_t* mask, oth_stream_t stream) {
+    if (!env) return fail(OTH_EINVAL, "NULL oth_env");
+    if (int rc = check_search_policy(opponent, "opponent")) return rc;
+    if (int rc = use_device(env)) return rc;
+    const uint64_t call = env->ply++;
+    return with_n(env->n, [&](auto NC) {
+        return launch_play_search<decltype(NC)::value>(env, OTH_PLAY_SEARCH_RESET_VS, opponent, opponent, 0, nullptr,
+                                                       protagonist, mask, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                                       nullptr, call, (hipStream_t)stream);
+    });
+}
+
+int oth_step_vs_search(oth_env* env, const oth_search_policy* opponent, const int32_t* actions,
+                       const int8_t* protagonist, int32_t* rewards, uint8_t* dones, int32_t* plies,
+                       int32_t* fallbacks, oth_stream_t stream) {
+    if (!env) return fail(OTH_EINVAL, "NULL oth_env");
+    if (int rc = check_search_policy(opponent, "opponent")) return rc;
+    if (!actions) return fail(OTH_EINVAL, "actions is NULL");
+    if (int rc = use_device(env)) return rc;
+    const uint64_t call = env->ply++;
+    return with_n(env->n, [&](auto NC) {
+        return launch_play_search<decltype(NC)::value>(env, OTH_PLAY_SEARCH_STEP_VS, opponent, opponent, 0, actions,
+                                                       protagonist, nullptr, nullptr, rewards, dones, nullptr, plies,
+                                                       fallbacks, call, (hipStream_t)stream);
+    });
+}
+
 int oth_reset_vs(oth_env* env, int32_t opponent_policy, const int8_t* protagonist, const uint8_t* mask,
                  oth_stream_t stream) {
     OTH_CHECK_ENV(env);

@@ -126,4 +126,14 @@ int launch_search(oth_env* env, int depth, const int8_t* weights, int mobility, 
                   int32_t* value, int32_t* best, int32_t* move_values, uint8_t* status, uint64_t* nodes,
                   hipStream_t st);
 
+// k_play_search (oth_play_search, oth_reset_vs_search, oth_step_vs_search) in play_search_n.hip, every N, a
+// unit of its own per board size.  mode: which of the three; the vs modes pass the opponent as both colours.
+// ctr: the first ply's counter (play) or the call's (vs).
+enum { OTH_PLAY_SEARCH_PLAY = 0, OTH_PLAY_SEARCH_STEP_VS = 1, OTH_PLAY_SEARCH_RESET_VS = 2 };
+template <int N>
+int launch_play_search(oth_env* env, int mode, const oth_search_policy* black, const oth_search_policy* white,
+                       int n_plies, const int32_t* act_in, const int8_t* prot, const uint8_t* mask, int32_t* actions,
+                       int32_t* rewards, uint8_t* dones, uint8_t* fb_ply, int32_t* plies, int32_t* fb_cnt,
+                       uint64_t ctr, hipStream_t st);
+
 }  // namespace oth_host

@@ -1,0 +1,423 @@
+// play_search.hpp -- the search as a player: oth_play_search (oth_step_policy
+// with the mover's move chosen by oth_search's computation, a configuration per
+// colour) and oth_reset_vs_search / oth_step_vs_search (oth_reset_vs /
+// oth_step_vs with the embedded opponent's move chosen so).  The spec is the
+// header's comment on oth_play_search.
+//
+// The searched move S(board, cfg): with e empty squares the search runs to
+// depth d = e when e <= cfg.endgame (every line then reaches a game end: the
+// move is oth_solve's), else to cfg.depth; a finished search plays its best
+// move, a search over its budget plays GreedyPolicy's move (the most flips, the
+// lowest square of equals) and the ply counts as a fallback.
+//
+// The shared core (the part outside __HIPCC__: the depth rule, the greedy key
+// by solve_flips popcounts and one board's move on the host) is plain host /
+// device code: tests/host/play_search_host.cpp compiles the same text with g++.
+//
+// Device mapping (k_play_search): k_search's -- a block of one wave over
+// SOLVE_GROUP boards, a lane per (board, root move) task, the tasks packed over
+// the lanes in 64-task chunks, value / best / over-budget reduced in LDS with
+// the 64-bit key, the per-lane SearchStack -- run in rounds:
+//   * the lanes < SOLVE_GROUP own their boards' Lane<N> state in registers for
+//     the whole call.  In a round every owner advances its board through
+//     everything that needs no search (the protagonist's ply, random-opening
+//     plies, a terminated board's plies, tallies, auto-reset: a per-board phase
+//     that only moves forward) until the board wants a searched move or is
+//     finished for this call, and publishes (mover, opponent, move mask, depth,
+//     which side's evaluation) to LDS;
+//   * after a barrier the wave reads the group's task count from LDS -- the
+//     loop's exit test is block-uniform -- and leaves when there is none;
+//   * otherwise it searches every task (depth, evaluation and budget per task:
+//     boards in endgame mode sit beside boards in depth mode, black movers
+//     beside white ones), reduces, and the owners apply S through step_lane.
+// Every round places a disc on every wanting board or finishes it, the rounds
+// are bounded by n_plies (play) or the board's phase sequence (vs), and every
+// search by max_nodes.
+#pragma once
+#include "search.hpp"
+
+namespace oth {
+
+// one colour's oth_search_policy as the kernel takes it (weights: device memory on the device)
+struct PlaySearchSide {
+    const int8_t* weights;
+    int depth, mobility, terminal, endgame;
+    uint32_t max_nodes;
+};
+
+// the discs the root places: all of them from `endgame` empty squares on (at least one: a board that is searched has a move)
+OTH_HD int play_search_depth(int empties, int depth, int endgame) {
+    const int d = empties <= endgame ? empties : depth;
+    return d < 1 ? 1 : d;
+}
+
+// GreedyPolicy's order on root moves (simple_policies.py:69-92): the max of
+// (flips << 8 | 255 - square) is the lowest square of the most flips
+template <int N>
+OTH_HD int play_search_flip_key(const BB<Geo<N>::W>& mover, const BB<Geo<N>::W>& opp, int a) {
+    return popcount(solve_flips<N>(mover, opp, a)) << 8 | (255 - a);
+}
+
+// S of one board on the host (the tests' host build): the move, -1 for a
+// terminated board and for a live one whose stored possible_moves is empty
+// (GreedyPolicy's None); *fallback: the search ran over its budget.
+template <int N>
+inline int play_search_move_host(const uint64_t* black, const uint64_t* white, const uint64_t* stored, uint32_t meta,
+                                 const PlaySearchSide& c, int* fallback) {
+    constexpr int W = Geo<N>::W, NN = N * N;
+    static_assert(NN <= 256, "a square fits the key's low byte");
+    BB<W> B, Wt, Lg;
+    for (int i = 0; i < W; ++i) {
+        B.w[i] = black[i];
+        Wt.w[i] = white[i];
+        Lg.w[i] = stored[i];
+    }
+    *fallback = 0;
+    int v0;
+    if (search_status<N>(B, Wt, Lg, meta, c.terminal, v0) != SEARCH_DONE) return -1;
+    const int d = play_search_depth(NN - popcount(B | Wt), c.depth, c.endgame);
+    int32_t value, best, mv[NN];
+    uint64_t nodes;
+    const int st = search_board_host<N>(black, white, stored, meta, d, c.weights, c.mobility, c.terminal, c.max_nodes,
+                                        &value, &best, mv, &nodes);
+    if (st == SEARCH_DONE) return best;
+    *fallback = 1;
+    const bool tw = (meta & 1u) != 0;
+    const BB<W> mover = tw ? Wt : B, opp = tw ? B : Wt;
+    BB<W> todo = Lg & Geo<N>::BOARD;
+    int key = 0;
+    while (any(todo)) {
+        const int a = lowest_square<W>(todo);
+        todo = todo & ~square<W>(a);
+        const int k = play_search_flip_key<N>(mover, opp, a);
+        key = k > key ? k : key;
+    }
+    return 255 - (key & 255);
+}
+
+}  // namespace oth
+
+#if defined(__HIPCC__)
+#include "vs.hpp"
+
+namespace oth_dev {
+
+constexpr int PS_PLAY = 0, PS_STEP_VS = 1, PS_RESET_VS = 2;
+// a board's phase in the vs modes (vs.hpp's control flow cut where it may need a search), in the order it is gone through
+constexpr int VS_PRE = 0,     // the opponent replies before the protagonist's ply
+    VS_PROT = 1,              // the protagonist's ply
+    VS_POST = 2,              // the opponent replies after it
+    VS_END = 3,               // plies, tallies, auto-reset
+    VS_RESET_REPLY = 4,       // the opponent's replies of a reset (no openings, nothing reported)
+    VS_DONE = 5;
+
+// MODE PS_PLAY: side_b is black's policy, side_w white's, ctr the first ply's counter; the vs modes: both are
+// the opponent's, ctr the call's counter.  same: both sides read one weight table (one plane set is built).
+// Outputs: actions / rewards / dones / fb_ply [n_plies][E] in play mode; rewards / dones / plies_out / fb_cnt [E]
+// in PS_STEP_VS; none in PS_RESET_VS (mask: the boards to reset, NULL for all).  Each may be NULL.
+template <int N, int MODE>
+__global__ __launch_bounds__(SOLVE_BLOCK) void k_play_search(
+    uint64_t* __restrict__ boards, uint16_t* __restrict__ meta, uint64_t* __restrict__ legal, int E, uint32_t flags,
+    PlaySearchSide side_b, PlaySearchSide side_w, int same, int n_plies, const int32_t* __restrict__ act_in,
+    const int8_t* __restrict__ prot, const uint8_t* __restrict__ mask, int32_t* __restrict__ actions,
+    int32_t* __restrict__ rewards, uint8_t* __restrict__ dones, uint8_t* __restrict__ fb_ply,
+    int32_t* __restrict__ plies_out, int32_t* __restrict__ fb_cnt, unsigned long long* __restrict__ wdl,
+    unsigned long long* __restrict__ wdl_vs, Rng rng, uint64_t ctr) {
+    constexpr int W = Geo<N>::W, NN = N * N, G = SOLVE_GROUP;
+    static_assert(NN <= 256, "a square fits the reduction keys' low byte");
+    static_assert(SOLVE_BLOCK == 64, "one ballot is one word of a plane");
+    __shared__ uint64_t g_planes[2][SEARCH_PLANES * W];
+    __shared__ uint64_t g_M[G][W], g_O[G][W], g_moves[G][W];  // a wanting board's mover, opponent and root moves
+    __shared__ int g_cnt[G];    // its tasks; 0: the board wants no search this round
+    __shared__ int g_depth[G], g_side[G];
+    __shared__ unsigned long long g_key[G];  // max of (value + INF) << 8 | (255 - square), as k_search
+    __shared__ int g_gkey[G];                // max of play_search_flip_key: the fallback's move
+    __shared__ unsigned int g_over[G];
+    ctr += *rng.ply_off;  // graph-region offset (oth_graph_end); 0 eagerly
+    const int lane = threadIdx.x;
+    const long long e0 = (long long)blockIdx.x * G;
+    const int ne = (int)(E - e0 < G ? E - e0 : G);
+    // the bit-planes of weights + 128 per colour: lane l holds square 64 k + l, one ballot per plane
+    auto build_planes = [&](const int8_t* __restrict__ weights, uint64_t* out) {
+#pragma unroll
+        for (int k = 0; k < W; ++k) {
+            const int a = 64 * k + lane;
+            const uint32_t u = a < NN ? (uint32_t)((int)weights[a] + 128) : 0u;
+#pragma unroll
+            for (int b = 0; b < SEARCH_PLANES; ++b) {
+                const unsigned long long m = __ballot((u >> b) & 1u);
+                if (lane == 0) out[b * W + k] = m;
+            }
+        }
+    };
+    build_planes(side_b.weights, g_planes[0]);
+    if (!same) build_planes(side_w.weights, g_planes[1]);  // (same: a kernel argument, uniform)
+    const uint64_t* planes_w = same ? g_planes[0] : g_planes[1];
+
+    // ---- the owners' state
+    bool owner = lane < ne;
+    const int e = (int)(e0 + (owner ? lane : 0));
+    if (MODE == PS_RESET_VS && owner && mask && !mask[e]) owner = false;
+    const uint32_t id = rng.id_base + (uint32_t)e;
+    const uint64_t gbase = ctr * VS_PLIES_PER_CALL;
+    const Solo<N> eng(0, nullptr);
+    Lane<N> s;
+    s.black = zero<W>();
+    s.white = zero<W>();
+    s.legal = zero<W>();
+    s.meta = M_TERMINATED;
+    bool protw = true;
+    int p = 0;                                                   // play: the board's next ply
+    int ph = VS_DONE, r = 0, d = 1, win = NO_DISK, plies = 0, nfb = 0;  // vs: phase and the call's results
+    uint32_t j = 0;                                              // vs: the call's next draw
+    uint32_t cb = 0, cd = 0, cw = 0, vw = 0, vd = 0, vl = 0;
+    if (owner) {
+        if (MODE != PS_PLAY) protw = prot ? prot[e] == WHITE_DISK : true;
+        if (MODE == PS_RESET_VS) {
+            reset_lane<N>(s, rng.seed, id, ctr, RNG_OPENING_RESET, rng.init_rand);
+            ph = VS_RESET_REPLY;
+        } else {
+            load_lane<N>(s, boards, meta, legal, e);
+            if (MODE == PS_STEP_VS && !(s.meta & M_TERMINATED)) {
+                d = 0;
+                ph = VS_PRE;
+            }
+        }
+    }
+    auto has_move = [&]() { return any(s.legal & Geo<N>::BOARD); };
+    // play: ply p's outputs
+    auto record = [&](int a, int rr, int dd, int fb) {
+        const size_t o = (size_t)p * (size_t)E + (size_t)e;
+        if (actions) actions[o] = a;
+        if (rewards) rewards[o] = rr;
+        if (dones) dones[o] = (uint8_t)dd;
+        if (fb_ply) fb_ply[o] = (uint8_t)fb;
+    };
+    // play: ply p of a live board (k_play's ply)
+    auto play_ply = [&](int a, int fb) {
+        int rr, dd, ww;
+        step_lane<N>(s, a, flags, rr, dd, ww, eng);
+        if (dd) {
+            count_winner(ww, cb, cd, cw);
+            if (flags & OTH_AUTO_RESET) reset_lane<N>(s, rng.seed, id, ctr + (uint64_t)p, RNG_OPENING_AUTO, rng.init_rand);
+        }
+        record(a, rr, dd, fb);
+        ++p;
+    };
+    // vs: one ply; a reset's replies report nothing (reset_vs_lane)
+    auto vs_ply = [&](int a) {
+        if (ph == VS_RESET_REPLY) {
+            int rr, dd, ww;
+            step_lane<N>(s, a, flags, rr, dd, ww, eng);
+        } else {
+            step_lane<N>(s, a, flags, r, d, win, eng);
+        }
+    };
+    // the board through everything that needs no search; true: it wants a searched move now
+    auto advance = [&]() -> bool {
+        if constexpr (MODE == PS_PLAY) {
+            while (p < n_plies) {
+                if (s.meta & M_TERMINATED) {
+                    record(-1, 0, 1, 0);
+                    ++p;
+                    continue;
+                }
+                if ((s.meta >> M_RAND_SHIFT) > 0) {  // a random-opening ply
+                    const int a = random_action<N>(s, action_draw(rng.seed, id, ctr + (uint64_t)p));
+                    s.meta -= 1u << M_RAND_SHIFT;
+                    play_ply(a, 0);
+                    continue;
+                }
+                if (!has_move()) {  // GreedyPolicy's None: the invalid path
+                    play_ply(-1, 0);
+                    continue;
+                }
+                return true;
+            }
+            return false;
+        } else {
+            for (;;) {
+                if (ph == VS_DONE) return false;
+                if (ph == VS_PROT) {
+                    int a = act_in[e];
+                    const uint64_t g = gbase + j++;
+                    if ((s.meta >> M_RAND_SHIFT) > 0) {  // opening ply: the protagonist's action is replaced too
+                        a = random_action<N>(s, action_draw(rng.seed, id, g));
+                        s.meta -= 1u << M_RAND_SHIFT;
+                    }
+                    step_lane<N>(s, a, flags, r, d, win, eng);
+                    ph = d ? VS_END : VS_POST;
+                    continue;
+                }
+                if (ph == VS_END) {
+                    plies = (int)j;
+                    ph = VS_DONE;
+                    if (d) {
+                        count_winner(win, cb, cd, cw);
+                        const int pcol = protw ? WHITE_DISK : BLACK_DISK;
+                        vw += win == pcol;
+                        vd += win == NO_DISK;
+                        vl += win == -pcol;
+                        if (flags & OTH_AUTO_RESET) {
+                            reset_lane<N>(s, rng.seed, id, ctr, RNG_OPENING_AUTO, rng.init_rand);
+                            ph = VS_RESET_REPLY;
+                        }
+                    }
+                    continue;
+                }
+                // the reply phases: the opponent moves while it is to move and the game is on
+                const bool term = (s.meta & M_TERMINATED) != 0;
+                if (term || ((s.meta & M_TURN_WHITE) != 0) == protw) {
+                    if (ph == VS_PRE && !term) {
+                        ph = VS_PROT;
+                    } else if (ph == VS_RESET_REPLY) {
+                        ph = VS_DONE;
+                    } else {  // the game ended before the protagonist's ply, or the replies after it are over
+                        r = -r;
+                        ph = VS_END;
+                    }
+                    continue;
+                }
+                if (ph != VS_RESET_REPLY && (s.meta >> M_RAND_SHIFT) > 0) {
+                    const int a = random_action<N>(s, action_draw(rng.seed, id, gbase + j++));
+                    s.meta -= 1u << M_RAND_SHIFT;
+                    vs_ply(a);
+                    continue;
+                }
+                if (!has_move()) {
+                    ++j;
+                    vs_ply(-1);
+                    continue;
+                }
+                return true;
+            }
+        }
+    };
+    // the searched move (or the fallback's) of a board that wanted one
+    auto apply = [&](int a, int fb) {
+        if constexpr (MODE == PS_PLAY) {
+            play_ply(a, fb);
+        } else {
+            ++j;
+            nfb += fb;
+            vs_ply(a);
+        }
+    };
+    if (lane < G) {
+#pragma unroll
+        for (int k = 0; k < W; ++k) g_M[lane][k] = g_O[lane][k] = g_moves[lane][k] = 0ull;
+        g_depth[lane] = 1;
+        g_side[lane] = 0;
+    }
+
+    // ---- the rounds
+    for (;;) {
+        bool want = false;
+        if (lane < G) {
+            if (owner) want = advance();
+            int cnt = 0;
+            if (want) {
+                const bool tw = (s.meta & M_TURN_WHITE) != 0;
+                const BB<W> M = pick(tw, s.white, s.black), O = pick(tw, s.black, s.white);
+                const BB<W> mv = s.legal & Geo<N>::BOARD;
+#pragma unroll
+                for (int k = 0; k < W; ++k) {
+                    g_M[lane][k] = M.w[k];
+                    g_O[lane][k] = O.w[k];
+                    g_moves[lane][k] = mv.w[k];
+                }
+                const bool sw = MODE == PS_PLAY && tw;
+                g_side[lane] = sw ? 1 : 0;
+                g_depth[lane] = play_search_depth(NN - popcount(M | O), sw ? side_w.depth : side_b.depth,
+                                                  sw ? side_w.endgame : side_b.endgame);
+                cnt = popcount(mv);
+            }
+            g_cnt[lane] = cnt;
+            g_key[lane] = 0ull;
+            g_gkey[lane] = 0;
+            g_over[lane] = 0u;
+        }
+        __syncthreads();
+        int pre[G + 1];  // the prefix of the group's task counts
+        pre[0] = 0;
+#pragma unroll
+        for (int i = 0; i < G; ++i) pre[i + 1] = pre[i] + g_cnt[i];
+        const int total = pre[G];
+        if (total == 0) break;  // block-uniform: read from LDS after the barrier
+        for (int base = 0; base < total; base += SOLVE_BLOCK) {  // block-uniform
+            const int t = base + lane;
+            const bool active = t < total;
+            int i = 0;  // the task's board: the last i with pre[i] <= t
+#pragma unroll
+            for (int k = 1; k < G; ++k) i += (active && t >= pre[k]) ? 1 : 0;
+            int first = 0;
+#pragma unroll
+            for (int k = 1; k < G; ++k) first = i >= k ? pre[k] : first;
+            BB<W> M, O, mv;
+#pragma unroll
+            for (int k = 0; k < W; ++k) {
+                M.w[k] = g_M[i][k];
+                O.w[k] = g_O[i][k];
+                mv.w[k] = g_moves[i][k];
+            }
+            const int a = active ? select_bit(mv, t - first) : 0;  // (t - first < popcount for an active lane)
+            const bool sw = g_side[i] != 0;
+            const int depth = g_depth[i];
+            const uint32_t max_nodes = sw ? side_w.max_nodes : side_b.max_nodes;
+            const SearchEval ev{sw ? planes_w : g_planes[0], sw ? side_w.mobility : side_b.mobility,
+                                sw ? side_w.terminal : side_b.terminal};
+            SolveTask<N> task;
+            search_task_init<N>(task, M, O, a);
+            task.live = active;
+            if (active) atomicMax(&g_gkey[i], play_search_flip_key<N>(M, O, a));
+            SearchStack<N> st;
+            while (__any(task.live))
+                if (task.live) search_step<N>(task, st, max_nodes, depth, ev);
+            if (active) {
+                if (task.over) atomicOr(&g_over[i], 1u);
+                else atomicMax(&g_key[i], (unsigned long long)(task.result + SEARCH_INF) << 8 | (unsigned long long)(255 - a));
+            }
+        }
+        __syncthreads();
+        if (want) {
+            const bool over = g_over[lane] != 0u;
+            apply(255 - (over ? g_gkey[lane] & 255 : (int)(g_key[lane] & 255ull)), over ? 1 : 0);
+        }
+    }
+
+    // ---- the boards back, the call's outputs, the tallies
+    if (owner) {
+        store_lane<N>(s, boards, meta, legal, e);
+        if (MODE == PS_STEP_VS) {
+            if (rewards) rewards[e] = r;
+            if (dones) dones[e] = (uint8_t)d;
+            if (plies_out) plies_out[e] = plies;
+            if (fb_cnt) fb_cnt[e] = nfb;
+        }
+    }
+    if (MODE != PS_RESET_VS) {
+        // two blocks share a W/D/L slot (the handle has one per 16 boards): atomics without a return value
+        const size_t slot = 4 * (size_t)(blockIdx.x >> 1);
+        cb = wave_sum(cb);
+        cd = wave_sum(cd);
+        cw = wave_sum(cw);
+        if (lane == 0 && wdl) {
+            if (cb) atomicAdd(wdl + slot + 0, (unsigned long long)cb);
+            if (cd) atomicAdd(wdl + slot + 1, (unsigned long long)cd);
+            if (cw) atomicAdd(wdl + slot + 2, (unsigned long long)cw);
+        }
+        if (MODE == PS_STEP_VS) {
+            vw = wave_sum(vw);
+            vd = wave_sum(vd);
+            vl = wave_sum(vl);
+            if (lane == 0 && wdl_vs) {
+                if (vw) atomicAdd(wdl_vs + slot + 0, (unsigned long long)vw);
+                if (vd) atomicAdd(wdl_vs + slot + 1, (unsigned long long)vd);
+                if (vl) atomicAdd(wdl_vs + slot + 2, (unsigned long long)vl);
+            }
+        }
+    }
+}
+
+}  // namespace oth_dev
+#endif

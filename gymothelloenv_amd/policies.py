@@ -15,6 +15,7 @@ import numpy as np
 
 from . import _lib as L
 from .othello import WHITE_DISK
+from .vec_env import SearchConfig  # noqa: F401  (SearchPolicy's batched counterpart: the search played on the device)
 
 PROTAGONIST_TURN = 1  # simple_policies.py:8-9
 OPPONENT_TURN = -1

@@ -245,6 +245,32 @@ class VecOthelloEnv(object):
                                           _ptr(dones), self._stream()), "oth_step_policy")
         return actions, rewards, dones
 
+    def play_search(self, black, white=None, n_plies=1, record=True, fallbacks=False):
+        """n_plies plies where every board's mover plays its colour's searched move
+        (oth_play_search): step_policy with the policy's move replaced by the
+        SearchConfig's -- `black` for black's plies, `white` (None: `black`) for
+        white's -- in one launch that never synchronises the host.  Random-opening
+        plies, terminated boards, auto-reset, the tallies and the ply counter are
+        step_policy's.
+
+        Returns (actions, rewards, dones) of shape (n_plies, E) (None if not
+        recorded), and with fallbacks=True a uint8 (n_plies, E) tensor that is 1
+        where the ply's search ran over max_nodes and GreedyPolicy moved."""
+        if not isinstance(black, SearchConfig) or not (white is None or isinstance(white, SearchConfig)):
+            raise TypeError("play_search takes SearchConfig objects")
+        n_plies = int(n_plies)
+        if n_plies < 1:
+            raise ValueError("n_plies must be >= 1")
+        pb = black._policy(self)
+        pw = pb if white is None or white is black else white._policy(self)
+        a = r = d = None
+        if record:
+            a, r, d = self._i32(n_plies, self.num_envs), self._i32(n_plies, self.num_envs), self._u8(n_plies, self.num_envs)
+        f = self._u8(n_plies, self.num_envs) if fallbacks else None
+        L.check(self._lib.oth_play_search(self._h, ctypes.addressof(pb), ctypes.addressof(pw), n_plies, _ptr(a),
+                                          _ptr(r), _ptr(d), _ptr(f), self._stream()), "oth_play_search")
+        return (a, r, d, f) if fallbacks else (a, r, d)
+
     # ------------------------------------------- OthelloEnv semantics on device
     def _protagonist(self, protagonist):
         if protagonist is None:
@@ -261,26 +287,51 @@ class VecOthelloEnv(object):
         """OthelloEnv.reset (othello.py:151-174) for every board: reset, then the
         embedded opponent (`opponent` = 'random' | 'greedy', played on the device)
         replies until the protagonist (+1 white, the reference default, or -1
-        black; int or per-board tensor) is to move."""
+        black; int or per-board tensor) is to move.  `opponent` may be a
+        SearchConfig: the opponent then plays its searched move (oth_reset_vs_search)."""
         prot = self._protagonist(protagonist)
         m = None if mask is None else mask.to(device=self.device, dtype=torch.uint8).contiguous()
+        if isinstance(opponent, SearchConfig):
+            L.check(self._lib.oth_reset_vs_search(self._h, ctypes.addressof(opponent._policy(self)), _ptr(prot),
+                                                  _ptr(m), self._stream()), "oth_reset_vs_search")
+            return self.get_observation()
         L.check(self._lib.oth_reset_vs(self._h, _POLICIES[opponent], _ptr(prot), _ptr(m), self._stream()),
                 "oth_reset_vs")
         return self.get_observation()
 
     def step_vs(self, actions, opponent="random", protagonist=None, observe=True, obs=None, obs_layout=None,
-                obs_dtype=torch.int64):
+                obs_dtype=torch.int64, fallbacks=False):
         """OthelloEnv.step (othello.py:176-200) for every board: the protagonist
         plays `actions`, the device opponent replies until the protagonist is to
         move again.  Returns (obs, rewards (protagonist's view, negated after an
         opponent ply ended the game), dones bool, plies applied per board).  The
         observation (get_observation's layout unless `obs_layout`; into `obs` if
-        given) comes from the same launch (oth_step_vs_observe)."""
+        given) comes from the same launch (oth_step_vs_observe).
+
+        `opponent` may be a SearchConfig: the opponent plays its searched move
+        (oth_step_vs_search, one launch, no host round trip per reply), the
+        observation comes from an observe launch after it, and with fallbacks=True
+        a fifth result counts, per board, the opponent's plies of this call whose
+        search ran over max_nodes and were played by GreedyPolicy (int32 (E,))."""
         prot = self._protagonist(protagonist)
         a = actions.to(device=self.device, dtype=torch.int32).contiguous()
         if a.numel() != self.num_envs:
             raise ValueError("expected %d actions, got %d" % (self.num_envs, a.numel()))
         r, d, n = self._i32(self.num_envs), self._u8(self.num_envs), self._i32(self.num_envs)
+        if isinstance(opponent, SearchConfig):
+            f = self._i32(self.num_envs) if fallbacks else None
+            o = None
+            if observe:
+                lay, o = self._obs_out(obs_layout, obs_dtype, obs)
+            L.check(self._lib.oth_step_vs_search(self._h, ctypes.addressof(opponent._policy(self)), _ptr(a),
+                                                 _ptr(prot), _ptr(r), _ptr(d), _ptr(n), _ptr(f), self._stream()),
+                    "oth_step_vs_search")
+            if observe:
+                L.check(self._lib.oth_observe(self._h, lay, _DTYPES[o.dtype], _ptr(o), self._stream()), "oth_observe")
+            res = (o, r, d.view(torch.bool), n)
+            return res + (f,) if fallbacks else res
+        if fallbacks:
+            raise ValueError("fallbacks are a search opponent's: pass a SearchConfig as opponent")
         if observe:
             lay, o = self._obs_out(obs_layout, obs_dtype, obs)
             L.check(self._lib.oth_step_vs_observe(self._h, _POLICIES[opponent], _ptr(a), _ptr(prot), _ptr(r),
@@ -511,16 +562,7 @@ class VecOthelloEnv(object):
             if getattr(self, "_default_w", None) is None:
                 self._default_w = default_search_weights(self.board_size).reshape(nn).to(self.device)
             return self._default_w
-        w = torch.as_tensor(weights)
-        if w.is_floating_point() or w.is_complex() or w.dtype == torch.bool:
-            raise ValueError("weights must be integers")
-        if w.numel() != nn or w.dim() not in (1, 2) or (w.dim() == 2 and w.shape[0] != self.board_size):
-            raise ValueError("weights must have shape (N, N) or (N*N,)")
-        if w.dtype != torch.int8:
-            if int(w.min()) < -128 or int(w.max()) > 127:
-                raise ValueError("weights must fit int8")
-            w = w.to(torch.int8)
-        return w.reshape(nn).to(self.device).contiguous()
+        return _int8_weights(weights, self.board_size).reshape(nn).to(self.device).contiguous()
 
     def search(self, depth, weights=None, mobility=0, terminal=64, max_nodes=1 << 22, best=False, move_values=False,
                status=False, nodes=False):
@@ -760,13 +802,82 @@ def _no_capture(what):
         raise RuntimeError("%s synchronises the device and cannot run during a HIP-graph capture" % what)
 
 
+def _int8_weights(weights, n=None):
+    """weights checked as VecOthelloEnv.search takes them: an integer tensor or
+    array that fits int8, of shape (N, N) or (N*N,) (N = n, or any board size
+    when n is None); returns it as an int8 host or device tensor."""
+    w = torch.as_tensor(weights)
+    if w.is_floating_point() or w.is_complex() or w.dtype == torch.bool:
+        raise ValueError("weights must be integers")
+    if n is None:
+        side = w.shape[0] if w.dim() == 2 else next((k for k in range(4, 17) if k * k == w.numel()), 0)
+    else:
+        side = n
+    if w.numel() != side * side or w.dim() not in (1, 2) or (w.dim() == 2 and w.shape[0] != side) or \
+            not 4 <= side <= 16:
+        raise ValueError("weights must have shape (N, N) or (N*N,)")
+    if w.dtype != torch.int8:
+        if int(w.min()) < -128 or int(w.max()) > 127:
+            raise ValueError("weights must fit int8")
+        w = w.to(torch.int8)
+    return w
+
+
+class SearchConfig(object):
+    """A search as a player (struct oth_search_policy): the move of a board with
+    e empty squares is oth_search's `best` at depth e when e <= endgame_empties
+    (every line then reaches a game end: the exact move), else at `depth`; where
+    the search runs over max_nodes (per root move) GreedyPolicy moves and the ply
+    counts as a fallback.  weights / mobility / terminal are VecOthelloEnv.search's
+    (None: default_search_weights(N)), checked here as there.  Used by
+    VecOthelloEnv.play_search and as `opponent` of reset_vs / step_vs.  The int8
+    weights are cached per device and board size, so a captured call copies nothing."""
+
+    def __init__(self, depth=4, weights=None, mobility=0, terminal=64, endgame_empties=0, max_nodes=1 << 22):
+        for name, v, lo, hi in (("depth", depth, 1, L.OTH_SEARCH_MAX_DEPTH), ("mobility", mobility, -127, 127),
+                                ("terminal", terminal, 1, 32767),
+                                ("endgame_empties", endgame_empties, 0, L.OTH_SEARCH_MAX_DEPTH),
+                                ("max_nodes", max_nodes, 1, 2 ** 32 - 1)):
+            if isinstance(v, bool) or int(v) != v:
+                raise ValueError("%s must be an integer" % name)
+            if not lo <= int(v) <= hi:
+                raise ValueError("%s must be in [%d, %d]" % (name, lo, hi))
+        self.depth, self.mobility, self.terminal = int(depth), int(mobility), int(terminal)
+        self.endgame_empties, self.max_nodes = int(endgame_empties), int(max_nodes)
+        self.weights = None if weights is None else _int8_weights(weights).clone()
+        self._cache = {}  # (device, N) -> (device weights, OthSearchPolicy)
+
+    def _policy(self, env):
+        """The struct for env's device and board size (built once, kept alive here)."""
+        key = (str(env.device), env.board_size)
+        hit = self._cache.get(key)
+        if hit is None:
+            if self.weights is None:
+                w = env._search_weights(None)
+            else:
+                w = env._search_weights(self.weights)
+            pol = L.OthSearchPolicy(w.data_ptr(), self.depth, self.mobility, self.terminal, self.endgame_empties,
+                                    self.max_nodes)
+            hit = self._cache[key] = (w, pol)
+        return hit[1]
+
+    def __repr__(self):
+        return "SearchConfig(depth=%d, weights=%s, mobility=%d, terminal=%d, endgame_empties=%d, max_nodes=%d)" % (
+            self.depth, "None" if self.weights is None else "<%d squares>" % self.weights.numel(), self.mobility,
+            self.terminal, self.endgame_empties, self.max_nodes)
+
+
 def default_search_weights(n):
     """The square weights VecOthelloEnv.search uses when it is given none: an int8
     (n, n) tensor on the host, by square class -- corner 100, X-square (a corner's
     diagonal neighbour) -50, C-square (a corner's orthogonal neighbour) -20, any
     other edge square 10, the rest 0; where the classes overlap on small boards
     the precedence is corner > X > C > edge.  A conventional shape, not a tuned
-    table: its playing strength is unmeasured."""
+    table.  Measured (tools/arena.py; 16,384 8x8 games per
+    pairing and colour, up to 10 random opening plies, the last 10 squares exact):
+    SearchConfig(depth=1) wins 92-99 % of its games against the random, greedy and
+    MaxiMin-3 movers, depth 4 wins 98-99.6 %; depth 4 beats depth 1 in 90 % of the
+    games as either colour, and depth 3 in 64 % as black but in 44 % as white."""
     n = int(n)
     w = torch.zeros(n, n, dtype=torch.int8)
     w[0, :] = w[-1, :] = 10

@@ -367,6 +367,62 @@ int oth_step_vs_observe(oth_env *env, int32_t opponent_policy, const int32_t *ac
                         int32_t *rewards, uint8_t *dones, int32_t *plies, int32_t layout, int32_t dtype, void *obs,
                         oth_stream_t stream);
 
+/* The search as a player: one colour's (or the embedded opponent's) move
+ * chooser.  The struct is host memory, read during the call; its values are
+ * baked into the launch, so the calls below stay capturable into a HIP graph.
+ *
+ * The searched move S(board, p).  With e the board's number of empty squares,
+ * d = e if e <= p.endgame_empties, else d = p.depth.  oth_search's computation
+ * runs on the board with depth d and p's weights, mobility_weight,
+ * terminal_weight and max_nodes (per root move); the root list is the board's
+ * stored possible_moves.  Status DONE: S is `best`.  Status ABORTED: S is
+ * oth_greedy_actions' move (the most flips, the lowest square of equals) and
+ * the ply counts as a *fallback*.  With d = e every line reaches a game end, so
+ * from endgame_empties squares on the move is oth_solve's `best` (a positive
+ * terminal_weight does not change the argmax). */
+typedef struct oth_search_policy {
+    const int8_t *weights;     /* DEVICE int8[N*N], as oth_search takes it */
+    int32_t depth;             /* [1, OTH_SEARCH_MAX_DEPTH] */
+    int32_t mobility_weight;   /* [-127, 127] */
+    int32_t terminal_weight;   /* [1, 32767] */
+    int32_t endgame_empties;   /* [0, OTH_SEARCH_MAX_DEPTH] */
+    uint64_t max_nodes;        /* [1, 2^32 - 1], per root move */
+} oth_search_policy;
+
+/* oth_step_policy with the policy's move replaced by S: black's plies use
+ * *black, white's *white (the two may be the same pointer; neither may be
+ * NULL).  Everything else is oth_step_policy's contract: a random move while
+ * random-opening plies remain, drawn for ply g = ply counter + p; an already
+ * terminated board gives action -1, done 1, reward 0; OTH_AUTO_RESET resets a
+ * board after its terminal ply; the tallies are oth_counts'; the ply counter
+ * advances by n_plies; inside a graph region the slot's ply offset is added.
+ * Outputs are [n_plies][E], each may be NULL, every element of a non-NULL
+ * output is written; fallbacks[p][e] is 1 where ply p of board e was an aborted
+ * search played by greedy, else 0.  A live board with an empty stored mask
+ * plays what oth_step_policy(OTH_POLICY_GREEDY) plays there (action -1).
+ *
+ * oth_reset_vs_search / oth_step_vs_search are oth_reset_vs / oth_step_vs with
+ * the opponent's policy move replaced by S(board, *opponent); the control flow,
+ * the draws (ply j of call c uses counter c*256 + j), the negated reward,
+ * plies, both tallies, the reset_vs-style OTH_AUTO_RESET and the one ply
+ * counter consumed per call are theirs.  fallbacks[e] (may be NULL) is the
+ * number of the opponent's plies of this call that were fallbacks, the replies
+ * of an auto-reset included.  For the observation, call oth_observe after it.
+ *
+ * One launch each (a wave per 8 boards, the boards' root moves over its
+ * lanes); no call synchronises the host.  OTH_EINVAL, checked before the
+ * handle is read and with nothing launched: a NULL handle, a NULL policy, NULL
+ * weights inside a policy, a field out of range, n_plies < 1, NULL actions in
+ * oth_step_vs_search. */
+int oth_play_search(oth_env *env, const oth_search_policy *black, const oth_search_policy *white,
+                    int32_t n_plies, int32_t *actions, int32_t *rewards, uint8_t *dones, uint8_t *fallbacks,
+                    oth_stream_t stream);
+int oth_reset_vs_search(oth_env *env, const oth_search_policy *opponent, const int8_t *protagonist,
+                        const uint8_t *mask, oth_stream_t stream);
+int oth_step_vs_search(oth_env *env, const oth_search_policy *opponent, const int32_t *actions,
+                       const int8_t *protagonist, int32_t *rewards, uint8_t *dones, int32_t *plies,
+                       int32_t *fallbacks, oth_stream_t stream);
+
 /* possible_moves of every env as masks uint64[E][W] (othello.py:242, :270, :466). */
 int oth_legal(oth_env *env, uint64_t *out, oth_stream_t stream);
 
