@@ -29,7 +29,7 @@ SIZES = list(range(4, 17))
 SOURCES = ("capi.hip", "kernels_n.hip", "play_rand_n.hip", "masked.hip", "device.hpp", "launch.hpp", "bitboard.hpp",
            "masked.hpp", "ply.hpp", "sample_step.hpp", "maximin_wave.hpp", "playouts_n.hip", "playouts.hpp",
            "tables.hpp", "state.hpp", "engines.hpp", "policy.hpp", "play.hpp", "vs.hpp", "observe.hpp", "solve_n.hip",
-           "solve.hpp", "search_n.hip", "search.hpp", "play_search_n.hip", "play_search.hpp")
+           "solve.hpp", "root_tasks.hpp", "search_n.hip", "search.hpp", "play_search_n.hip", "play_search.hpp")
 PLAY_SIZES = list(range(4, 12))  # k_play_rand (one-word boards) and k_play_rand_w (two-word boards)
 # play_rand_n.hip: the max-ILP machine scheduler (one wave per SIMD: latency hidden by the schedule
 # counts, occupancy does not); the rest of the library keeps the default scheduler

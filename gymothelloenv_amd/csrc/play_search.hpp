@@ -14,10 +14,10 @@
 // by solve_flips popcounts and one board's move on the host) is plain host /
 // device code: tests/host/play_search_host.cpp compiles the same text with g++.
 //
-// Device mapping (k_play_search): k_search's -- a block of one wave over
-// SOLVE_GROUP boards, a lane per (board, root move) task, the tasks packed over
-// the lanes in 64-task chunks, value / best / over-budget reduced in LDS with
-// the 64-bit key, the per-lane SearchStack -- run in rounds:
+// Device mapping (k_play_search): root_tasks.hpp's run_tasks (a block of one
+// wave over SOLVE_GROUP boards, a lane per (board, root move) task, the tasks
+// packed over the lanes in 64-task chunks) over search_step, the tasks loaded
+// from LDS, the best move / over-budget reduced there with root_key, in rounds:
 //   * the lanes < SOLVE_GROUP own their boards' Lane<N> state in registers for
 //     the whole call.  In a round every owner advances its board through
 //     everything that needs no search (the protagonist's ply, random-opening
@@ -125,33 +125,19 @@ __global__ __launch_bounds__(SOLVE_BLOCK) void k_play_search(
     unsigned long long* __restrict__ wdl_vs, Rng rng, uint64_t ctr) {
     constexpr int W = Geo<N>::W, NN = N * N, G = SOLVE_GROUP;
     static_assert(NN <= 256, "a square fits the reduction keys' low byte");
-    static_assert(SOLVE_BLOCK == 64, "one ballot is one word of a plane");
     __shared__ uint64_t g_planes[2][SEARCH_PLANES * W];
     __shared__ uint64_t g_M[G][W], g_O[G][W], g_moves[G][W];  // a wanting board's mover, opponent and root moves
     __shared__ int g_cnt[G];    // its tasks; 0: the board wants no search this round
     __shared__ int g_depth[G], g_side[G];
-    __shared__ unsigned long long g_key[G];  // max of (value + INF) << 8 | (255 - square), as k_search
+    __shared__ unsigned long long g_key[G];  // max of root_key
     __shared__ int g_gkey[G];                // max of play_search_flip_key: the fallback's move
     __shared__ unsigned int g_over[G];
     ctr += *rng.ply_off;  // graph-region offset (oth_graph_end); 0 eagerly
     const int lane = threadIdx.x;
     const long long e0 = (long long)blockIdx.x * G;
     const int ne = (int)(E - e0 < G ? E - e0 : G);
-    // the bit-planes of weights + 128 per colour: lane l holds square 64 k + l, one ballot per plane
-    auto build_planes = [&](const int8_t* __restrict__ weights, uint64_t* out) {
-#pragma unroll
-        for (int k = 0; k < W; ++k) {
-            const int a = 64 * k + lane;
-            const uint32_t u = a < NN ? (uint32_t)((int)weights[a] + 128) : 0u;
-#pragma unroll
-            for (int b = 0; b < SEARCH_PLANES; ++b) {
-                const unsigned long long m = __ballot((u >> b) & 1u);
-                if (lane == 0) out[b * W + k] = m;
-            }
-        }
-    };
-    build_planes(side_b.weights, g_planes[0]);
-    if (!same) build_planes(side_w.weights, g_planes[1]);  // (same: a kernel argument, uniform)
+    build_planes<N>(side_b.weights, g_planes[0]);  // the evaluation's planes per colour
+    if (!same) build_planes<N>(side_w.weights, g_planes[1]);  // (same: a kernel argument, uniform)
     const uint64_t* planes_w = same ? g_planes[0] : g_planes[1];
 
     // ---- the owners' state
@@ -338,50 +324,33 @@ __global__ __launch_bounds__(SOLVE_BLOCK) void k_play_search(
             g_over[lane] = 0u;
         }
         __syncthreads();
-        int pre[G + 1];  // the prefix of the group's task counts
-        pre[0] = 0;
+        // the tasks: depth, evaluation and budget are their board's.  The count is read from LDS after the
+        // barrier: the exit test is block-uniform
+        const int total = run_tasks<N, SearchFrame<N>>(
+            g_moves, g_cnt,
+            [&](int i, int a, bool active, BB<W>& M, BB<W>& O) {
 #pragma unroll
-        for (int i = 0; i < G; ++i) pre[i + 1] = pre[i] + g_cnt[i];
-        const int total = pre[G];
-        if (total == 0) break;  // block-uniform: read from LDS after the barrier
-        for (int base = 0; base < total; base += SOLVE_BLOCK) {  // block-uniform
-            const int t = base + lane;
-            const bool active = t < total;
-            int i = 0;  // the task's board: the last i with pre[i] <= t
-#pragma unroll
-            for (int k = 1; k < G; ++k) i += (active && t >= pre[k]) ? 1 : 0;
-            int first = 0;
-#pragma unroll
-            for (int k = 1; k < G; ++k) first = i >= k ? pre[k] : first;
-            BB<W> M, O, mv;
-#pragma unroll
-            for (int k = 0; k < W; ++k) {
-                M.w[k] = g_M[i][k];
-                O.w[k] = g_O[i][k];
-                mv.w[k] = g_moves[i][k];
-            }
-            const int a = active ? select_bit(mv, t - first) : 0;  // (t - first < popcount for an active lane)
-            const bool sw = g_side[i] != 0;
-            const int depth = g_depth[i];
-            const uint32_t max_nodes = sw ? side_w.max_nodes : side_b.max_nodes;
-            const SearchEval ev{sw ? planes_w : g_planes[0], sw ? side_w.mobility : side_b.mobility,
-                                sw ? side_w.terminal : side_b.terminal};
-            SolveTask<N> task;
-            search_task_init<N>(task, M, O, a);
-            task.live = active;
-            if (active) atomicMax(&g_gkey[i], play_search_flip_key<N>(M, O, a));
-            SearchStack<N> st;
-            while (__any(task.live))
-                if (task.live) search_step<N>(task, st, max_nodes, depth, ev);
-            if (active) {
-                if (task.over) atomicOr(&g_over[i], 1u);
-                else atomicMax(&g_key[i], (unsigned long long)(task.result + SEARCH_INF) << 8 | (unsigned long long)(255 - a));
-            }
-        }
+                for (int k = 0; k < W; ++k) {
+                    M.w[k] = g_M[i][k];
+                    O.w[k] = g_O[i][k];
+                }
+                if (active) atomicMax(&g_gkey[i], play_search_flip_key<N>(M, O, a));
+                const bool sw = g_side[i] != 0;
+                const int depth = g_depth[i];
+                const uint32_t max_nodes = sw ? side_w.max_nodes : side_b.max_nodes;
+                const SearchEval ev{sw ? planes_w : g_planes[0], sw ? side_w.mobility : side_b.mobility,
+                                    sw ? side_w.terminal : side_b.terminal};
+                return [=](RootTask<N>& s, uint32_t* st) { search_step<N>(s, st, max_nodes, depth, ev); };
+            },
+            [&](const RootTask<N>& s, int i, int a) {
+                if (s.over) atomicOr(&g_over[i], 1u);
+                else atomicMax(&g_key[i], root_key(s.result, SEARCH_INF, a));
+            });
+        if (total == 0) break;
         __syncthreads();
         if (want) {
             const bool over = g_over[lane] != 0u;
-            apply(255 - (over ? g_gkey[lane] & 255 : (int)(g_key[lane] & 255ull)), over ? 1 : 0);
+            apply(over ? 255 - (g_gkey[lane] & 255) : root_key_square(g_key[lane]), over ? 1 : 0);
         }
     }
 

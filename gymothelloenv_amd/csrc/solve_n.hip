@@ -17,10 +17,8 @@ template <int N>
 int launch_solve(oth_env* env, int max_empties, uint32_t max_nodes, int32_t* value, int32_t* best,
                  int32_t* move_values, uint8_t* status, uint64_t* nodes, hipStream_t st) {
     const long long groups = ((long long)env->E + SOLVE_GROUP - 1) / SOLVE_GROUP;
-    // dynamic LDS: none, or in the OTH_SOLVE_LDS_STACK arm max_empties stack levels a lane (<= 25,088 bytes)
-    launch_k(k_solve<N>, dim3((unsigned)groups), dim3(SOLVE_BLOCK), solve_lds_bytes<N>(max_empties), st, env->boards,
-             env->meta, env->legal, env->E, max_empties, max_nodes, value, best, move_values, status,
-             reinterpret_cast<unsigned long long*>(nodes));
+    launch_k(k_solve<N>, dim3((unsigned)groups), dim3(SOLVE_BLOCK), 0, st, env->boards, env->meta, env->legal, env->E,
+             max_empties, max_nodes, value, best, move_values, status, reinterpret_cast<unsigned long long*>(nodes));
     return after_launch("oth_solve");
 }
 

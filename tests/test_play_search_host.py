@@ -22,7 +22,7 @@ ROOT = os.path.dirname(HERE)
 SRC = os.path.join(HERE, "host", "play_search_host.cpp")
 LIB = os.path.join(HERE, "host", "libplay_search_host.so")
 HDRS = [os.path.join(ROOT, "gymothelloenv_amd", "csrc", f)
-        for f in ("play_search.hpp", "search.hpp", "solve.hpp", "bitboard.hpp")]
+        for f in ("play_search.hpp", "search.hpp", "root_tasks.hpp", "bitboard.hpp")]
 SIZES = [4, 5, 6, 8, 10, 16]
 
 

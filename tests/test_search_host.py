@@ -16,7 +16,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 SRC = os.path.join(HERE, "host", "search_host.cpp")
 LIB = os.path.join(HERE, "host", "libsearch_host.so")
-HDRS = [os.path.join(ROOT, "gymothelloenv_amd", "csrc", f) for f in ("search.hpp", "solve.hpp", "bitboard.hpp")]
+HDRS = [os.path.join(ROOT, "gymothelloenv_amd", "csrc", f) for f in ("search.hpp", "root_tasks.hpp", "bitboard.hpp")]
 BIG = 1 << 24  # a budget no test position reaches
 SIZES = [4, 5, 6, 8, 10, 16]
 WSETS = ["default", "random", "ones"]

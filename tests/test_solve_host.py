@@ -17,7 +17,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 SRC = os.path.join(HERE, "host", "solve_host.cpp")
 LIB = os.path.join(HERE, "host", "libsolve_host.so")
-HDRS = [os.path.join(ROOT, "gymothelloenv_amd", "csrc", f) for f in ("solve.hpp", "bitboard.hpp")]
+HDRS = [os.path.join(ROOT, "gymothelloenv_amd", "csrc", f) for f in ("solve.hpp", "root_tasks.hpp", "bitboard.hpp")]
 BIG = 1 << 24  # a budget no test position reaches
 
 

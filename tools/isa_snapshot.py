@@ -7,13 +7,14 @@ unchanged:
     python tools/isa_snapshot.py /tmp/isa_before
     ... edit ...
     python tools/isa_snapshot.py /tmp/isa_after
-    python tools/isa_snapshot.py --compare /tmp/isa_before /tmp/isa_after
+    python tools/isa_snapshot.py --compare [--brief] /tmp/isa_before /tmp/isa_after
 
 The compare mode goes kernel symbol by kernel symbol (code and kernel descriptor,
 block labels renumbered per function so that a kernel added or removed elsewhere
 in the unit does not show up in its neighbours), prints `identical` or the number
 of differing lines with the differing lines themselves, and exits non-zero if
-anything differs.
+anything differs.  --brief counts a unit's identical symbols on one line and
+leaves the differing lines out: a record short enough to commit.
 """
 import concurrent.futures
 import difflib
@@ -32,6 +33,8 @@ def units():
     u += [("kernels_n.hip", "kernels_n%d" % n, ["-DOTH_N=%d" % n]) for n in B.SIZES]
     u += [("play_rand_n.hip", "play_rand_n%d" % n, ["-DOTH_N=%d" % n] + B.play_flags()) for n in B.PLAY_SIZES]
     u += [("playouts_n.hip", "playouts_n%d" % n, ["-DOTH_N=%d" % n] + B.PLAYOUT_FLAGS) for n in B.SIZES]
+    for src in ("solve_n", "search_n", "play_search_n"):
+        u += [(src + ".hip", "%s%d" % (src, n), ["-DOTH_N=%d" % n]) for n in B.SIZES]
     return u
 
 
@@ -77,7 +80,7 @@ def symbols(text):
     return syms
 
 
-def compare(dir_a, dir_b, show=40):
+def compare(dir_a, dir_b, show=40, brief=False):
     names = sorted(set(os.listdir(dir_a)) | set(os.listdir(dir_b)))
     total = differing = 0
     for name in (n for n in names if n.endswith(".s")):
@@ -85,11 +88,14 @@ def compare(dir_a, dir_b, show=40):
         for d in (dir_a, dir_b):
             path = os.path.join(d, name)
             sides.append(symbols(open(path).read()) if os.path.exists(path) else {})
+        same = 0
         for sym in sorted(set(sides[0]) | set(sides[1])):
             a, b = sides[0].get(sym), sides[1].get(sym)
             total += 1
             if a == b:
-                print("%s %s: identical" % (name[:-2], sym))
+                same += 1
+                if not brief:
+                    print("%s %s: identical" % (name[:-2], sym))
                 continue
             differing += 1
             if a is None or b is None:
@@ -97,17 +103,23 @@ def compare(dir_a, dir_b, show=40):
                 continue
             delta = [x for x in difflib.unified_diff(a, b, lineterm="", n=0) if not x.startswith(("---", "+++"))]
             print("%s %s: %d lines differ" % (name[:-2], sym, sum(1 for x in delta if x[0] in "+-")))
+            if brief:
+                continue
             for x in delta[:show]:
                 print("    " + x)
             if len(delta) > show:
                 print("    ... (%d more)" % (len(delta) - show))
+        if brief:
+            print("%s: %d of %d symbols identical" % (name[:-2], same, len(set(sides[0]) | set(sides[1]))))
     print("%d kernel symbols compared, %d differ" % (total, differing))
     return 1 if differing else 0
 
 
 def main():
     if sys.argv[1] == "--compare":
-        sys.exit(compare(sys.argv[2], sys.argv[3]))
+        brief = "--brief" in sys.argv
+        dirs = [x for x in sys.argv[2:] if x != "--brief"]
+        sys.exit(compare(dirs[0], dirs[1], brief=brief))
     outdir = sys.argv[1]
     os.makedirs(outdir, exist_ok=True)
     with concurrent.futures.ThreadPoolExecutor(8) as ex:

@@ -12,6 +12,9 @@ region).  Recorded, not asserted: milliseconds per call (median, min, max over
 the repetitions) and the share of fused plies played by the greedy fallback.
 
     python tools/probe_play_search.py [--out profiles/play_search/probe.json] [--reps 5]
+        [--lib another_build.so]
+
+--lib times another build of the library (an A/B arm) in place of the shipped one.
 """
 import argparse
 import json
@@ -47,12 +50,14 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "play_search", "probe.json"))
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--lib", help="another build of the library (an A/B variant)")
     a = ap.parse_args()
     import torch
-    from gymothelloenv_amd import SearchConfig, VecOthelloEnv
+    from gymothelloenv_amd import SearchConfig, VecOthelloEnv, _lib
+    lib = _lib.load_path(a.lib) if a.lib else None
     dev = torch.device("cuda", 0)
     stream = torch.cuda.current_stream(dev)
-    env = VecOthelloEnv(BOARDS, board_size=N, seed=EMPTIES, device=dev)
+    env = VecOthelloEnv(BOARDS, board_size=N, seed=EMPTIES, device=dev, lib=lib)
     env.reset()
     env.step_policy("random", n_plies=N * N - 4 - EMPTIES, record=False)  # a ply places a disc
     b, m, lg = env.get_state()
@@ -91,7 +96,8 @@ def main():
     env.close()
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "w") as f:
-        json.dump({"device": torch.cuda.get_device_name(0), "reps": a.reps, "rows": rows}, f, indent=1)
+        json.dump({"device": torch.cuda.get_device_name(0), "reps": a.reps, "lib": a.lib or "shipped", "rows": rows}, f,
+                  indent=1)
         f.write("\n")
 
 

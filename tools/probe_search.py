@@ -15,6 +15,9 @@ MaxiMin-3 movers (oth_step_vs's embedded opponents), colours split evenly, after
 opponent replays one game per colour).  Recorded, not asserted.
 
     python tools/probe_search.py [--out profiles/search/probe.json] [--skip-strength] [--skip-time]
+        [--lib another_build.so]
+
+--lib times another build of the library (an A/B arm) in place of the shipped one.
 """
 import argparse
 import json
@@ -51,11 +54,12 @@ def timed(torch, stream, fn, reps):
 
 def time_part(torch, a):
     from gymothelloenv_amd import OthelloLibError, VecOthelloEnv, _lib
+    lib = _lib.load_path(a.lib) if a.lib else None
     dev = torch.device("cuda", 0)
     stream = torch.cuda.current_stream(dev)
     rows = []
     for empties in EMPTIES:
-        env = VecOthelloEnv(BOARDS, board_size=N, seed=empties, device=dev)
+        env = VecOthelloEnv(BOARDS, board_size=N, seed=empties, device=dev, lib=lib)
         env.reset()
         env.step_policy("random", n_plies=N * N - 4 - empties, record=False)  # a ply places a disc
         b, m, lg = env.get_state()
@@ -86,7 +90,8 @@ def time_part(torch, a):
 
 
 def strength_part(torch, a):
-    from gymothelloenv_amd import VecOthelloEnv
+    from gymothelloenv_amd import VecOthelloEnv, _lib
+    lib = _lib.load_path(a.lib) if a.lib else None
     dev = torch.device("cuda", 0)
     rows = []
     prot = torch.where(torch.arange(GAMES) % 2 == 0, 1, -1).to(torch.int8)  # white, black, white, ...
@@ -94,7 +99,8 @@ def strength_part(torch, a):
         for depth in STRENGTH_DEPTHS:
             t0 = time.time()
             # random opening plies: without them two deterministic movers play two games, one per colour
-            env = VecOthelloEnv(GAMES, board_size=N, seed=100 + depth, initial_rand_steps=OPENING_PLIES, device=dev)
+            env = VecOthelloEnv(GAMES, board_size=N, seed=100 + depth, initial_rand_steps=OPENING_PLIES, device=dev,
+                                lib=lib)
             env.reset_vs(opp, protagonist=prot)
             calls = 0
             while not bool(env.terminated().all()):
@@ -117,11 +123,12 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "search", "probe.json"))
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--maximin-depth", type=int, default=5, help="the deepest MaxiMin timed beside the search")
+    ap.add_argument("--lib", help="another build of the library (an A/B variant)")
     ap.add_argument("--skip-time", action="store_true")
     ap.add_argument("--skip-strength", action="store_true")
     a = ap.parse_args()
     import torch
-    res = {"device": torch.cuda.get_device_name(0), "reps": a.reps}
+    res = {"device": torch.cuda.get_device_name(0), "reps": a.reps, "lib": a.lib or "shipped"}
     if not a.skip_time:
         res["time"] = time_part(torch, a)
     if not a.skip_strength:

@@ -7,8 +7,8 @@ of boards whose search ran over the default node budget (status ABORTED).
 
     python tools/probe_solve.py [--out profiles/solve/probe.json] [--lib another_build.so]
 
---lib times another build of the library (an A/B arm, e.g. the unit built with
--DOTH_SOLVE_LDS_STACK=0: the stack in a per-lane array) in place of the shipped one.
+--lib times another build of the library (an A/B arm, e.g. the parent commit's
+built in a worktree) in place of the shipped one.
 """
 import argparse
 import ctypes
@@ -29,7 +29,7 @@ N = 8
 def host_lib():
     src = os.path.join(ROOT, "tests", "host", "solve_host.cpp")
     lib = os.path.join(ROOT, "tests", "host", "libsolve_host.so")
-    hdrs = [os.path.join(ROOT, "gymothelloenv_amd", "csrc", f) for f in ("solve.hpp", "bitboard.hpp")]
+    hdrs = [os.path.join(ROOT, "gymothelloenv_amd", "csrc", f) for f in ("solve.hpp", "root_tasks.hpp", "bitboard.hpp")]
     if not os.path.exists(lib) or os.path.getmtime(lib) < max(os.path.getmtime(p) for p in [src] + hdrs):
         subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-o", lib, src])
     L = ctypes.CDLL(lib)
