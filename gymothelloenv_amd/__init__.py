@@ -8,7 +8,8 @@ terminal/score) as HIP kernels for gfx950 behind a C ABI
     OthelloBaseEnv,          drop-in single-board classes with the
     SimpleOthelloEnv,        reference's constructor / attributes / 4-tuple step
     OthelloEnv
-    RandomPolicy, GreedyPolicy, MaxiMinPolicy, MonteCarloPolicy, SolverPolicy, SearchPolicy,
+    RandomPolicy, GreedyPolicy, MaxiMinPolicy, MonteCarloPolicy, MCTSPolicy, SolverPolicy,
+    SearchPolicy,
     make_state, undo_state
     default_search_weights   the conventional square weights of VecOthelloEnv.search
     SearchConfig             a search as a player: VecOthelloEnv.play_search, and the
@@ -28,8 +29,8 @@ def __getattr__(name):
     if name in ("OthelloBaseEnv", "SimpleOthelloEnv", "OthelloEnv"):
         from . import othello
         return getattr(othello, name)
-    if name in ("RandomPolicy", "GreedyPolicy", "MaxiMinPolicy", "MonteCarloPolicy", "SolverPolicy",
-                "SearchPolicy"):
+    if name in ("RandomPolicy", "GreedyPolicy", "MaxiMinPolicy", "MonteCarloPolicy", "MCTSPolicy",
+                "SolverPolicy", "SearchPolicy"):
         from . import policies
         return getattr(policies, name)
     if name in ("masked_sample", "masked_log_prob"):

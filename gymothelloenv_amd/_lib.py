@@ -43,6 +43,9 @@ OTH_SOLVE_EXACT, OTH_SOLVE_TERMINATED, OTH_SOLVE_SKIPPED, OTH_SOLVE_NO_MOVE, OTH
 OTH_SEARCH_MAX_DEPTH = 14  # oth_search
 OTH_SEARCH_NO_VALUE = -2 ** 31
 OTH_SEARCH_DONE, OTH_SEARCH_TERMINATED, OTH_SEARCH_NO_MOVE, OTH_SEARCH_ABORTED = 0, 1, 3, 4
+OTH_MCTS_MAX_ITERATIONS, OTH_MCTS_MAX_PLAYOUTS, OTH_MCTS_MAX_C = 65535, 64, 65535  # oth_mcts
+OTH_MCTS_MAX_TREE_NODES = 1 << 24
+OTH_MCTS_DONE, OTH_MCTS_TERMINATED, OTH_MCTS_NO_MOVE = 0, 1, 3
 OTH_GRAPH_SLOTS = 64
 OTH_GRAPH_COUNTER_SHIFT = 40
 
@@ -81,6 +84,17 @@ class OthSearchPolicy(ctypes.Structure):
                 ("max_nodes", ctypes.c_uint64)]
 
 
+class OthMctsParams(ctypes.Structure):
+    """struct oth_mcts_params (include/othello_mi355x.h): host memory read during the call."""
+    _fields_ = [("iterations", ctypes.c_int32),
+                ("playouts", ctypes.c_int32),
+                ("c_explore", ctypes.c_int32),
+                ("max_tree_nodes", ctypes.c_int32),
+                ("seed", ctypes.c_uint64),
+                ("id_key", ctypes.c_uint32),
+                ("counter", ctypes.c_uint64)]
+
+
 # every symbol include/othello_mi355x.h declares: (restype, argtypes)
 _P = ctypes.c_void_p
 _I32, _U32, _U64, _I64 = ctypes.c_int32, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_int64
@@ -95,6 +109,8 @@ SIGNATURES = {
     "oth_playouts": (_I32, [_P, _I32, _I32, _U64, _U32, _U64, _P, _P, _P, _P]),
     "oth_solve": (_I32, [_P, _I32, _U64, _P, _P, _P, _P, _P, _P]),
     "oth_search": (_I32, [_P, _I32, _P, _I32, _I32, _U64, _P, _P, _P, _P, _P, _P]),
+    "oth_mcts_workspace_bytes": (_I32, [_I32, _I32, _I32, _P]),
+    "oth_mcts": (_I32, [_P, _P, _P, _U64, _P, _P, _P, _P, _P, _P]),
     "oth_play_search": (_I32, [_P, _P, _P, _I32, _P, _P, _P, _P, _P]),
     "oth_reset_vs_search": (_I32, [_P, _P, _P, _P, _P]),
     "oth_step_vs_search": (_I32, [_P, _P, _P, _P, _P, _P, _P, _P, _P]),

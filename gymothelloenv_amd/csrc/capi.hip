@@ -421,6 +421,42 @@ int oth_solve(oth_env* env, int32_t max_empties, uint64_t max_nodes, int32_t* va
     });
 }
 
+int oth_mcts_workspace_bytes(int32_t board_size, int32_t n_envs, int32_t max_tree_nodes, uint64_t* bytes) {
+    if (!bytes) return fail(OTH_EINVAL, "bytes is NULL");
+    if (board_size < 4 || board_size > 16) return fail(OTH_EINVAL, "board_size must be in [4, 16]");
+    if (n_envs < 1) return fail(OTH_EINVAL, "n_envs must be >= 1");
+    if (max_tree_nodes < board_size * board_size || max_tree_nodes > OTH_MCTS_MAX_TREE_NODES)
+        return fail(OTH_EINVAL, "max_tree_nodes must be in [N*N, 2^24]");
+    *bytes = (uint64_t)n_envs * (uint64_t)max_tree_nodes * (uint64_t)mcts_node_words(board_size) * 8u;
+    return OTH_OK;
+}
+
+int oth_mcts(oth_env* env, const oth_mcts_params* p, void* workspace, uint64_t workspace_bytes, int32_t* visits,
+             int32_t* wins2, int32_t* best, int32_t* tree_nodes, uint8_t* status, oth_stream_t stream) {
+    // what needs no handle to decide comes first; all of it before the device is touched
+    if (!p) return fail(OTH_EINVAL, "params is NULL");
+    if (!workspace) return fail(OTH_EINVAL, "workspace is NULL");
+    if (!visits) return fail(OTH_EINVAL, "visits is NULL");
+    if (p->iterations < 1 || p->iterations > OTH_MCTS_MAX_ITERATIONS)
+        return fail(OTH_EINVAL, "iterations must be in [1, 65535]");
+    if (p->playouts < 1 || p->playouts > OTH_MCTS_MAX_PLAYOUTS) return fail(OTH_EINVAL, "playouts must be in [1, 64]");
+    if (p->c_explore < 0 || p->c_explore > OTH_MCTS_MAX_C) return fail(OTH_EINVAL, "c_explore must be in [0, 65535]");
+    if (p->max_tree_nodes < 16 || p->max_tree_nodes > OTH_MCTS_MAX_TREE_NODES)
+        return fail(OTH_EINVAL, "max_tree_nodes must be in [N*N, 2^24]");
+    if (p->counter >> 56) return fail(OTH_EINVAL, "counter must be below 2^56");
+    if (reinterpret_cast<uintptr_t>(workspace) & 7u) return fail(OTH_EINVAL, "workspace must be 8-byte aligned");
+    if (!env) return fail(OTH_EINVAL, "NULL oth_env");
+    uint64_t need = 0;
+    if (int rc = oth_mcts_workspace_bytes(env->n, env->E, p->max_tree_nodes, &need)) return rc;
+    if (workspace_bytes < need)
+        return fail(OTH_EINVAL, "workspace_bytes is below what oth_mcts_workspace_bytes reports");
+    if (int rc = use_device(env)) return rc;
+    return with_n(env->n, [&](auto NC) {
+        return launch_mcts<decltype(NC)::value>(env, p, workspace, visits, wins2, best, tree_nodes, status,
+                                                (hipStream_t)stream);
+    });
+}
+
 int oth_search(oth_env* env, int32_t depth, const int8_t* weights, int32_t mobility_weight, int32_t terminal_weight,
                uint64_t max_nodes, int32_t* value, int32_t* best, int32_t* move_values, uint8_t* status,
                uint64_t* nodes, oth_stream_t stream) {

@@ -136,4 +136,11 @@ int launch_play_search(oth_env* env, int mode, const oth_search_policy* black, c
                        int32_t* rewards, uint8_t* dones, uint8_t* fb_ply, int32_t* plies, int32_t* fb_cnt,
                        uint64_t ctr, hipStream_t st);
 
+// k_mcts (oth_mcts) in mcts_n.hip, every N, a unit of its own per board size.  The arguments are checked.
+template <int N>
+int launch_mcts(oth_env* env, const oth_mcts_params* p, void* workspace, int32_t* visits, int32_t* wins2,
+                int32_t* best, int32_t* tree_nodes, uint8_t* status, hipStream_t st);
+// the 64-bit words of one tree node (mcts.hpp MctsTree::WORDS): three boards of W words, v | w, the links, k | turn
+constexpr int mcts_node_words(int n) { return 3 * ((n * n + 63) / 64) + 3; }
+
 }  // namespace oth_host

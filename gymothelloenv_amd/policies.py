@@ -153,6 +153,41 @@ class MonteCarloPolicy(object):
         return self.get_action(obs)
 
 
+class MCTSPolicy(object):
+    """Monte-Carlo tree search move selection (no reference counterpart: the rung
+    after MonteCarloPolicy): the most visited root move of a UCT-style tree search
+    on the device (oth_mcts) with `iterations` descents, `playouts` random games
+    per evaluated node and exploration constant c.  Playouts are keyed by `seed`
+    and a call counter that moves on with every move, so a seeded policy replays
+    its games move for move."""
+
+    def __init__(self, iterations=256, playouts=8, c=1.0, seed=0):
+        self.env = None
+        self.iterations, self.playouts, self.c = int(iterations), int(playouts), float(c)
+        self._seed = int(seed)
+        self.counter = 0
+
+    def reset(self, env):
+        self.env = _base(env)
+
+    def seed(self, seed):
+        self._seed = int(seed)
+        self.counter = 0
+
+    def get_action(self, obs):
+        vec = self.env._vec
+        self.env._sync()
+        a = int(vec.mcts_actions(self.iterations, playouts=self.playouts, c=self.c, seed=self._seed,
+                                 counter=self.counter).cpu()[0])
+        self.counter += 1
+        if a < 0:
+            raise ValueError('no possible moves')
+        return a
+
+    def get_test_action(self, obs):
+        return self.get_action(obs)
+
+
 class SolverPolicy(object):
     """Perfect endgame play (no reference counterpart): once the board has at most
     max_empties empty squares the move is the exact solver's `best` (oth_solve: the
@@ -222,4 +257,4 @@ class SearchPolicy(object):
         return self.get_action(obs)
 
 
-__all__ = ['RandomPolicy', 'GreedyPolicy', 'MaxiMinPolicy', 'MonteCarloPolicy', 'SolverPolicy', 'SearchPolicy', 'PROTAGONIST_TURN', 'OPPONENT_TURN', 'WHITE_DISK']
+__all__ = ['RandomPolicy', 'GreedyPolicy', 'MaxiMinPolicy', 'MonteCarloPolicy', 'MCTSPolicy', 'SolverPolicy', 'SearchPolicy', 'PROTAGONIST_TURN', 'OPPONENT_TURN', 'WHITE_DISK']

@@ -90,6 +90,7 @@ class VecOthelloEnv(object):
         self._okobs = None  # (obs tensor, layout) step() / sample_step() have checked
         self._sample_calls = 0  # Philox counter of sample_actions
         self._playout_calls = 0  # `counter` of the next playouts() call that gives none
+        self._mcts_ws = None  # mcts()'s workspace: a uint8 tensor, regrown only when too small
         self._region_resets = None  # resets inside an open graph region (None: no region)
 
     # ------------------------------------------------------------------ utils
@@ -515,6 +516,76 @@ class VecOthelloEnv(object):
     @playout_counter.setter
     def playout_counter(self, v):
         self._playout_calls = int(v)
+
+    # ------------------------------------------------------ Monte-Carlo tree search
+    def mcts(self, iterations, playouts=8, c=1.0, max_tree_nodes=None, seed=None, id_key=0, counter=None,
+             wins2=False, best=False, tree_nodes=False, status=False):
+        """A UCT-style tree search with random-playout leaf evaluation from every
+        board's position (oth_mcts; include/othello_mi355x.h defines every output in
+        integers): `iterations` descents, each evaluating one node with `playouts`
+        (<= 64) random games, exploration constant c (round(256 c) in the key).  The
+        boards, the ply counter and the tallies are left untouched.
+
+        Returns visits, then wins2, best, tree_nodes and status when asked (the
+        header's order), as tensors on this device:
+          visits     int32 (E, N*N): the iterations through the root's child on each
+                     square, 0 without a child -- the visit-count policy target;
+          wins2      int32 (E, N*N): 2 wins + draws of the playouts backed up through
+                     it, for the side to move at the root;
+          best       int32 (E,): the most visited child (then the larger wins2, then
+                     the lowest square), -1 without a possible move;
+          tree_nodes int32 (E,): node slots the board's tree used;
+          status     uint8 (E,): OTH_MCTS_DONE / TERMINATED / NO_MOVE.
+        max_tree_nodes (per board) bounds the tree: a node whose children do not fit
+        stays a leaf.  None: max(N*N, iterations (N*N - 4) / 4), clipped to the C
+        ABI's maximum -- an iteration reserves at most one node's children.  This
+        default started as a guess; tools/probe_mcts.py then found 8,185 8x8 mid-game
+        boards at 64 iterations using 57 to 320 of its 960 slots, and one board at
+        4,096 iterations 13,147 of 61,440, so it is 3 to 7
+        times what those boards need; other board sizes are unmeasured.  The workspace
+        (oth_mcts_workspace_bytes) is a cached uint8 tensor, regrown only when too
+        small, so a warm call allocates nothing but its outputs and is capturable.
+        seed=None / counter=None: as playouts() -- the env's seed XOR
+        PLAYOUT_SEED_XOR, and `playout_counter`, which then moves on by one."""
+        E, nn = self.num_envs, self.board_size * self.board_size
+        I = int(iterations)
+        if max_tree_nodes is None:
+            max_tree_nodes = min(max(nn, I * (nn - 4) // 4), L.OTH_MCTS_MAX_TREE_NODES)
+        key = (self.seed ^ PLAYOUT_SEED_XOR if seed is None else int(seed)) & (2 ** 64 - 1)
+        own = counter is None
+        ctr = self._playout_calls if own else int(counter)
+        cx = int(round(256 * float(c)))
+        for name, v in (("iterations", I), ("playouts", int(playouts)), ("c", cx),
+                        ("max_tree_nodes", int(max_tree_nodes))):
+            if not -2 ** 31 <= v < 2 ** 31:
+                raise ValueError("%s is out of range" % name)
+        if not 0 <= ctr < 2 ** 64:
+            raise ValueError("counter is out of range")
+        p = L.OthMctsParams(I, int(playouts), cx, int(max_tree_nodes), key, int(id_key) & 0xffffffff, ctr)
+        need = ctypes.c_uint64(0)
+        L.check(self._lib.oth_mcts_workspace_bytes(self.board_size, E, p.max_tree_nodes, ctypes.byref(need)),
+                "oth_mcts_workspace_bytes")
+        if self._mcts_ws is None or self._mcts_ws.numel() < need.value:
+            self._mcts_ws = None  # (the old one goes first)
+            self._mcts_ws = torch.empty(need.value, dtype=torch.uint8, device=self.device)
+        vis = self._i32(E, nn)
+        w2 = self._i32(E, nn) if wins2 else None
+        bt = self._i32(E) if best else None
+        tn = self._i32(E) if tree_nodes else None
+        stt = self._u8(E) if status else None
+        L.check(self._lib.oth_mcts(self._h, ctypes.byref(p), _ptr(self._mcts_ws), self._mcts_ws.numel(), _ptr(vis),
+                                   _ptr(w2), _ptr(bt), _ptr(tn), _ptr(stt), self._stream()), "oth_mcts")
+        if own:
+            self._playout_calls += 1
+        res = (vis,) + tuple(t for t in (w2, bt, tn, stt) if t is not None)
+        return res[0] if len(res) == 1 else res
+
+    def mcts_actions(self, iterations, **kw):
+        """Every board's most visited root move of mcts(iterations, **kw) (its `best`):
+        int32 (E,), -1 for a board without a possible move."""
+        for k in ("wins2", "best", "tree_nodes", "status"):
+            kw.pop(k, None)
+        return self.mcts(iterations, best=True, **kw)[1]
 
     # ------------------------------------------------------------ exact endgame
     def solve(self, max_empties=10, max_nodes=1 << 22, best=False, move_values=False, status=False, nodes=False):

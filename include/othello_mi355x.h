@@ -340,6 +340,112 @@ int oth_search(oth_env *env, int32_t depth, const int8_t *weights, int32_t mobil
                int32_t terminal_weight, uint64_t max_nodes, int32_t *value, int32_t *best,
                int32_t *move_values, uint8_t *status, uint64_t *nodes, oth_stream_t stream);
 
+/* Monte-Carlo tree search per board (no reference counterpart: the rung after
+ * oth_playouts' flat Monte-Carlo): a UCT-style tree whose leaves are evaluated
+ * by random playouts, one launch for all boards, the tree in a workspace the
+ * caller supplies.  Every output is defined in integers below; the mapping to
+ * lanes shows in none of them.
+ *
+ * Parameters (struct oth_mcts_params, host memory, read during the call and
+ * baked into the launch): I iterations, R playouts per evaluated node, the
+ * exploration constant C in 1/256, T node slots per board, and the Philox key
+ * (seed, id_key, counter) of the playouts -- not the handle's.
+ *
+ * The tree.  A node holds a position as oth_step with flags 0 leaves it: both
+ * colours' discs, the side to move and the terminated bit.  A pass is already
+ * resolved in it: after a move whose reply is a pass the same colour is to move
+ * in the child.  A node also holds
+ *   v  the iterations that went through it, and
+ *   w  the sum, over the playouts backed up through it, of 2 [won] + [drawn],
+ *      counted for the colour that moved into the node -- the side that
+ *      chooses among it and its siblings.  No sign is flipped anywhere, passes
+ *      included.
+ * Node 0 is the board's position and used = 1.  The root's move list is the
+ * handle's stored possible_moves[e], as oth_step, oth_playouts (MOVES) and
+ * oth_solve treat it; below the root, moves are recomputed from the discs.
+ *
+ * Iteration i = 0 .. I-1 starts with cur = the root:
+ *  1. Descend.  Repeat:
+ *       - cur is terminated: stop.
+ *       - k = cur's move count.  If cur has no reservation yet: if used + k > T,
+ *         cur stays a leaf for the rest of the call: stop.  Otherwise it
+ *         reserves the k consecutive slots used .. used+k-1 for its children in
+ *         ascending square order, and used += k.
+ *       - cur has made fewer than k children: make the next one -- the lowest
+ *         square not yet made, oth_step's ply with flags 0 -- in its reserved
+ *         slot, move to it and stop.
+ *       - otherwise move to the child c of the largest key, the lowest square
+ *         among equal keys:
+ *           key = floor(2^15 w_c / (v_c R)) + floor(C isqrt(2^16 v_p) / (1 + v_c))
+ *         v_p is cur's v before this iteration's backup (for the root, i);
+ *         isqrt is the exact integer floor square root.  Everything fits 64-bit
+ *         integers: w_c <= 2^23, C isqrt(..) < 2^32; v_c >= 1 always, since a
+ *         node is evaluated in the iteration that makes it.  T >= N*N guarantees
+ *         that the root can always reserve.
+ *  2. Evaluate cur with R playouts.  Playout r is exactly one ROOT-mode playout
+ *     of oth_playouts started from cur's position: uniformly random legal moves
+ *     to the end, the same pass and game-end handling.  Playout ply p draws
+ *     Philox4x32-10, purpose 0, key `seed`, counter g = counter * 256 + p (word
+ *     g % 4 of block g / 4), with the id
+ *         id_key + ((env_id_base + e) I + i) R + r   (mod 2^32),
+ *     a function of the global env id, the iteration and r alone: a sharded run
+ *     equals the unsharded one.  A terminated cur counts as R playouts that all
+ *     end with its own final board.
+ *  3. Back up.  Every node on the path, the root included: v += 1.  Every node
+ *     but the root: w += 2 (playouts won by the colour that moved into it) +
+ *     (playouts drawn).
+ *
+ * Outputs (device pointers; visits is required, the others may be NULL; every
+ * element of every non-NULL output is written, nothing needs zeroing):
+ * visits int32[E][N*N], wins2 int32[E][N*N], best int32[E], tree_nodes
+ * int32[E], status uint8[E].  By status (oth_solve's numbers):
+ *   DONE        visits[a] / wins2[a] are the v / w of the root's child on
+ *               square a, 0 for squares without a child (outside the stored
+ *               mask, or not yet made when I < k); best is the root child with
+ *               the most visits, then the larger wins2, then the lowest square;
+ *               tree_nodes is used.
+ *   TERMINATED  meta bit 1 set; NO_MOVE: live, stored possible_moves empty.
+ *               visits / wins2 all 0, best -1, tree_nodes 1; nothing is searched.
+ *
+ * Workspace.  Device memory of at least oth_mcts_workspace_bytes(board_size,
+ * n_envs, T) bytes, 8-byte aligned; it needs no initialising and its contents
+ * after the call are unspecified (tree reuse between calls is not offered).
+ * oth_mcts_workspace_bytes needs no handle and no GPU; OTH_EINVAL for a board
+ * size outside [4, 16], n_envs < 1, T outside [N*N, OTH_MCTS_MAX_TREE_NODES] or
+ * a NULL bytes.
+ *
+ * Handle state.  The call reads boards, meta and the stored possible_moves and
+ * writes nothing of the handle: boards, meta, possible_moves, the ply counter,
+ * the graph offsets and both tallies stay as they are.  It only enqueues work,
+ * never synchronises the host and is capturable into a HIP graph; a replay
+ * repeats the same search (the graph regions' offsets are not used).  The
+ * running time is bounded whatever the input: I iterations of a descent that
+ * places a disc per level plus playouts of at most N*N plies.
+ *
+ * OTH_EINVAL, with nothing launched: NULL params / workspace / visits, a field
+ * out of range (these before the handle is looked at), a NULL handle,
+ * max_tree_nodes below N*N, workspace_bytes below what
+ * oth_mcts_workspace_bytes reports, a misaligned workspace.  Every board size
+ * works. */
+#define OTH_MCTS_MAX_ITERATIONS 65535
+#define OTH_MCTS_MAX_PLAYOUTS   64
+#define OTH_MCTS_MAX_C          65535
+#define OTH_MCTS_MAX_TREE_NODES (1 << 24)
+enum { OTH_MCTS_DONE = 0, OTH_MCTS_TERMINATED = 1, OTH_MCTS_NO_MOVE = 3 };
+typedef struct oth_mcts_params {
+    int32_t  iterations;      /* I in [1, OTH_MCTS_MAX_ITERATIONS] */
+    int32_t  playouts;        /* R in [1, OTH_MCTS_MAX_PLAYOUTS]: random games per evaluated node */
+    int32_t  c_explore;       /* C in [0, OTH_MCTS_MAX_C]: exploration constant in 1/256 */
+    int32_t  max_tree_nodes;  /* T in [N*N, OTH_MCTS_MAX_TREE_NODES]: node slots per board */
+    uint64_t seed;            /* Philox key of the playouts (not the handle's) */
+    uint32_t id_key;
+    uint64_t counter;         /* < 2^56, as oth_playouts */
+} oth_mcts_params;
+int oth_mcts_workspace_bytes(int32_t board_size, int32_t n_envs, int32_t max_tree_nodes, uint64_t *bytes);
+int oth_mcts(oth_env *env, const oth_mcts_params *p, void *workspace, uint64_t workspace_bytes,
+             int32_t *visits, int32_t *wins2, int32_t *best, int32_t *tree_nodes, uint8_t *status,
+             oth_stream_t stream);
+
 /* OthelloEnv (othello.py:96-214) for every env: the protagonist's colour per
  * env (protagonist: device int8[E] of +1 white / -1 black, NULL = all white,
  * the reference default) and an embedded opponent played on the device
