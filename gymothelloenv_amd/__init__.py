@@ -8,13 +8,16 @@ terminal/score) as HIP kernels for gfx950 behind a C ABI
     OthelloBaseEnv,          drop-in single-board classes with the
     SimpleOthelloEnv,        reference's constructor / attributes / 4-tuple step
     OthelloEnv
-    RandomPolicy, GreedyPolicy, MaxiMinPolicy, MonteCarloPolicy, MCTSPolicy, SolverPolicy,
-    SearchPolicy,
+    RandomPolicy, GreedyPolicy, MaxiMinPolicy, MonteCarloPolicy, MCTSPolicy, PUCTPolicy,
+    SolverPolicy, SearchPolicy,
     make_state, undo_state
     default_search_weights   the conventional square weights of VecOthelloEnv.search
     SearchConfig             a search as a player: VecOthelloEnv.play_search, and the
                              opponent of reset_vs / step_vs
     masked_sample, masked_log_prob   policy-head sampling over legal squares
+    puct_quantize, PuctLeaves,       the network-guided tree search of VecOthelloEnv.puct_begin /
+    uniform_evaluator,               puct_advance / puct_result / puct_search: a network's floats as the
+    playout_evaluator                search's integers, its leaves, and two evaluators without a network
 """
 from ._lib import LIB_PATH, OthelloLibError, load  # noqa: F401
 
@@ -23,14 +26,15 @@ BLACK_DISK, NO_DISK, WHITE_DISK = -1, 0, 1
 
 def __getattr__(name):
     # lazy: importing the package must not touch the GPU (build() runs on CPU hosts)
-    if name in ("VecOthelloEnv", "legal_moves", "default_search_weights", "SearchConfig"):
+    if name in ("VecOthelloEnv", "legal_moves", "default_search_weights", "SearchConfig", "PuctLeaves",
+                "puct_quantize", "uniform_evaluator", "playout_evaluator"):
         from . import vec_env
         return getattr(vec_env, name)
     if name in ("OthelloBaseEnv", "SimpleOthelloEnv", "OthelloEnv"):
         from . import othello
         return getattr(othello, name)
     if name in ("RandomPolicy", "GreedyPolicy", "MaxiMinPolicy", "MonteCarloPolicy", "MCTSPolicy",
-                "SolverPolicy", "SearchPolicy"):
+                "PUCTPolicy", "SolverPolicy", "SearchPolicy"):
         from . import policies
         return getattr(policies, name)
     if name in ("masked_sample", "masked_log_prob"):

@@ -46,6 +46,9 @@ OTH_SEARCH_DONE, OTH_SEARCH_TERMINATED, OTH_SEARCH_NO_MOVE, OTH_SEARCH_ABORTED =
 OTH_MCTS_MAX_ITERATIONS, OTH_MCTS_MAX_PLAYOUTS, OTH_MCTS_MAX_C = 65535, 64, 65535  # oth_mcts
 OTH_MCTS_MAX_TREE_NODES = 1 << 24
 OTH_MCTS_DONE, OTH_MCTS_TERMINATED, OTH_MCTS_NO_MOVE = 0, 1, 3
+OTH_PUCT_VALUE_ONE, OTH_PUCT_PRIOR_MAX, OTH_PUCT_MAX_C = 32768, 65535, 65535  # oth_puct_*
+OTH_PUCT_MAX_TREE_NODES, OTH_PUCT_MAX_SIMS = 1 << 24, (1 << 24) - 1
+OTH_PUCT_LEAF_NONE, OTH_PUCT_LEAF_EXPAND, OTH_PUCT_LEAF_VALUE, OTH_PUCT_LEAF_TERMINAL = range(4)
 OTH_GRAPH_SLOTS = 64
 OTH_GRAPH_COUNTER_SHIFT = 40
 
@@ -95,6 +98,24 @@ class OthMctsParams(ctypes.Structure):
                 ("counter", ctypes.c_uint64)]
 
 
+class OthPuctParams(ctypes.Structure):
+    """struct oth_puct_params (include/othello_mi355x.h): host memory read during the call."""
+    _fields_ = [("c_puct", ctypes.c_int32),
+                ("max_tree_nodes", ctypes.c_int32)]
+
+
+class OthPuctLeaves(ctypes.Structure):
+    """struct oth_puct_leaves (include/othello_mi355x.h): host memory holding device
+    addresses, each may be NULL."""
+    _fields_ = [("kind", ctypes.c_void_p),
+                ("boards", ctypes.c_void_p),
+                ("meta", ctypes.c_void_p),
+                ("legal", ctypes.c_void_p),
+                ("obs", ctypes.c_void_p),
+                ("layout", ctypes.c_int32),
+                ("dtype", ctypes.c_int32)]
+
+
 # every symbol include/othello_mi355x.h declares: (restype, argtypes)
 _P = ctypes.c_void_p
 _I32, _U32, _U64, _I64 = ctypes.c_int32, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_int64
@@ -111,6 +132,10 @@ SIGNATURES = {
     "oth_search": (_I32, [_P, _I32, _P, _I32, _I32, _U64, _P, _P, _P, _P, _P, _P]),
     "oth_mcts_workspace_bytes": (_I32, [_I32, _I32, _I32, _P]),
     "oth_mcts": (_I32, [_P, _P, _P, _U64, _P, _P, _P, _P, _P, _P]),
+    "oth_puct_workspace_bytes": (_I32, [_I32, _I32, _I32, _P]),
+    "oth_puct_begin": (_I32, [_P, _P, _P, _U64, _P, _P]),
+    "oth_puct_advance": (_I32, [_P, _P, _P, _U64, _P, _P, _I32, _P, _P]),
+    "oth_puct_result": (_I32, [_P, _P, _P, _U64, _P, _P, _P, _P, _P, _P]),
     "oth_play_search": (_I32, [_P, _P, _P, _I32, _P, _P, _P, _P, _P]),
     "oth_reset_vs_search": (_I32, [_P, _P, _P, _P, _P]),
     "oth_step_vs_search": (_I32, [_P, _P, _P, _P, _P, _P, _P, _P, _P]),

@@ -457,6 +457,78 @@ int oth_mcts(oth_env* env, const oth_mcts_params* p, void* workspace, uint64_t w
     });
 }
 
+int oth_puct_workspace_bytes(int32_t board_size, int32_t n_envs, int32_t max_tree_nodes, uint64_t* bytes) {
+    if (!bytes) return fail(OTH_EINVAL, "bytes is NULL");
+    if (board_size < 4 || board_size > 16) return fail(OTH_EINVAL, "board_size must be in [4, 16]");
+    if (n_envs < 1) return fail(OTH_EINVAL, "n_envs must be >= 1");
+    if (max_tree_nodes < board_size * board_size || max_tree_nodes > OTH_PUCT_MAX_TREE_NODES)
+        return fail(OTH_EINVAL, "max_tree_nodes must be in [N*N, 2^24]");
+    *bytes = puct_workspace_words(board_size, (uint64_t)n_envs, (uint64_t)max_tree_nodes) * 8u;
+    return OTH_OK;
+}
+
+namespace {
+
+// What the three oth_puct calls share, in oth_mcts' order: what needs no handle to decide first, all of it
+// before the device is touched.
+int puct_check(const oth_env* env, const oth_puct_params* p, const void* workspace, uint64_t workspace_bytes,
+               const oth_puct_leaves* leaves) {
+    if (!p) return fail(OTH_EINVAL, "params is NULL");
+    if (!workspace) return fail(OTH_EINVAL, "workspace is NULL");
+    if (p->c_puct < 0 || p->c_puct > OTH_PUCT_MAX_C) return fail(OTH_EINVAL, "c_puct must be in [0, 65535]");
+    if (p->max_tree_nodes < 16 || p->max_tree_nodes > OTH_PUCT_MAX_TREE_NODES)
+        return fail(OTH_EINVAL, "max_tree_nodes must be in [N*N, 2^24]");
+    if (reinterpret_cast<uintptr_t>(workspace) & 7u) return fail(OTH_EINVAL, "workspace must be 8-byte aligned");
+    if (leaves && leaves->obs) {
+        if (leaves->layout < OTH_OBS_BOARD || leaves->layout > OTH_OBS_LEGAL)
+            return fail(OTH_EINVAL, "unknown layout of the leaves' obs");
+        if (leaves->dtype < OTH_I8 || leaves->dtype > OTH_BF16)
+            return fail(OTH_EINVAL, "unknown dtype of the leaves' obs");
+    }
+    if (!env) return fail(OTH_EINVAL, "NULL oth_env");
+    uint64_t need = 0;
+    if (int rc = oth_puct_workspace_bytes(env->n, env->E, p->max_tree_nodes, &need)) return rc;
+    if (workspace_bytes < need)
+        return fail(OTH_EINVAL, "workspace_bytes is below what oth_puct_workspace_bytes reports");
+    return OTH_OK;
+}
+
+}  // namespace
+
+int oth_puct_begin(oth_env* env, const oth_puct_params* p, void* workspace, uint64_t workspace_bytes,
+                   const oth_puct_leaves* leaves, oth_stream_t stream) {
+    if (int rc = puct_check(env, p, workspace, workspace_bytes, leaves)) return rc;
+    if (int rc = use_device(env)) return rc;
+    return with_n(env->n, [&](auto NC) {
+        return launch_puct_begin<decltype(NC)::value>(env, p, workspace, leaves, (hipStream_t)stream);
+    });
+}
+
+int oth_puct_advance(oth_env* env, const oth_puct_params* p, void* workspace, uint64_t workspace_bytes,
+                     const int32_t* priors, const int32_t* values, int32_t more, const oth_puct_leaves* leaves,
+                     oth_stream_t stream) {
+    if (!priors) return fail(OTH_EINVAL, "priors is NULL");
+    if (!values) return fail(OTH_EINVAL, "values is NULL");
+    if (int rc = puct_check(env, p, workspace, workspace_bytes, leaves)) return rc;
+    if (int rc = use_device(env)) return rc;
+    return with_n(env->n, [&](auto NC) {
+        return launch_puct_advance<decltype(NC)::value>(env, p, workspace, priors, values, more, leaves,
+                                                        (hipStream_t)stream);
+    });
+}
+
+int oth_puct_result(oth_env* env, const oth_puct_params* p, void* workspace, uint64_t workspace_bytes,
+                    int32_t* visits, int64_t* value_sums, int32_t* best, int32_t* tree_nodes, uint8_t* status,
+                    oth_stream_t stream) {
+    if (!visits) return fail(OTH_EINVAL, "visits is NULL");
+    if (int rc = puct_check(env, p, workspace, workspace_bytes, nullptr)) return rc;
+    if (int rc = use_device(env)) return rc;
+    return with_n(env->n, [&](auto NC) {
+        return launch_puct_result<decltype(NC)::value>(env, p, workspace, visits, value_sums, best, tree_nodes, status,
+                                                       (hipStream_t)stream);
+    });
+}
+
 int oth_search(oth_env* env, int32_t depth, const int8_t* weights, int32_t mobility_weight, int32_t terminal_weight,
                uint64_t max_nodes, int32_t* value, int32_t* best, int32_t* move_values, uint8_t* status,
                uint64_t* nodes, oth_stream_t stream) {

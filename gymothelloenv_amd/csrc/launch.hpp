@@ -143,4 +143,23 @@ int launch_mcts(oth_env* env, const oth_mcts_params* p, void* workspace, int32_t
 // the 64-bit words of one tree node (mcts.hpp MctsTree::WORDS): three boards of W words, v | w, the links, k | turn
 constexpr int mcts_node_words(int n) { return 3 * ((n * n + 63) / 64) + 3; }
 
+// k_puct_begin / k_puct_advance / k_puct_result (oth_puct_*) in puct_n.hip, every N, a unit of its own per
+// board size.  The arguments are checked.  A non-NULL obs of the leaves is a second launch (launch_observe on
+// the workspace's leaf arrays).
+template <int N>
+int launch_puct_begin(oth_env* env, const oth_puct_params* p, void* workspace, const oth_puct_leaves* leaves,
+                      hipStream_t st);
+template <int N>
+int launch_puct_advance(oth_env* env, const oth_puct_params* p, void* workspace, const int32_t* priors,
+                        const int32_t* values, int more, const oth_puct_leaves* leaves, hipStream_t st);
+template <int N>
+int launch_puct_result(oth_env* env, const oth_puct_params* p, void* workspace, int32_t* visits, int64_t* value_sums,
+                       int32_t* best, int32_t* tree_nodes, uint8_t* status, hipStream_t st);
+// the 64-bit words of a search's workspace (puct.hpp PuctWs): a tag and a pad, two header words a board, the
+// leaves' boards, moves and meta in exchange format, then T nodes a board of three boards of W words and four more
+constexpr uint64_t puct_workspace_words(int n, uint64_t E, uint64_t T) {
+    return 2u + 2u * E + 3u * (uint64_t)((n * n + 63) / 64) * E + (E + 3u) / 4u +
+           E * T * (uint64_t)(3 * ((n * n + 63) / 64) + 4);
+}
+
 }  // namespace oth_host

@@ -1,0 +1,472 @@
+// puct.hpp -- oth_puct_begin / _advance / _result: a tree search per board whose
+// leaves are evaluated outside the library (a policy and value network between
+// launches), one simulation per launch for all boards (the spec is the header's
+// comment on oth_puct_begin: every output is an integer function of the board,
+// the parameters and the integers supplied).
+//
+// The workspace, in 64-bit words (PuctWs; E boards, T nodes a board):
+//   [0]                   the tag of the search that began here (puct_tag)
+//   [1]                   unused (keeps what follows 16-byte aligned in itself)
+//   [2, 2 + 2E)           a board's header: used | pending leaf << 32, then
+//                         kind | status << 8 | (the handle's meta at begin) << 32
+//   then [E][2W], [E][W]  the pending leaves' boards and moves, exchange format:
+//   and ceil(E / 4)       their meta (uint16 [E]); the observation kernels read these
+//   then E T WORDS        the trees
+// A node is PuctTree<N>::WORDS words:
+//   [0, W)      black's discs            [W, 2W)  white's
+//   [2W, 3W)    the node's moves (the side to move's; none: terminated)
+//   [3W]        w, an int64
+//   [3W + 1]    v | P << 32
+//   [3W + 2]    first child | parent << 32
+//   [3W + 3]    k | (turn | made << 1 | terminated << 2 | square << 8) << 32
+// first child 0: no children reserved (slot 0 is the root, never a child).  A
+// child exists from its parent's expansion on (square, P, v = w = 0, its parent);
+// its position words are written when a selection first moves to it (made).
+// Every node index is a whole 32-bit half of its word, as mcts.hpp's (its
+// header comment has the reason).  A node keeps its parent's index: the backup
+// walks the links and the path needs no array.
+//
+// The part outside __HIPCC__ is plain host/device code over bitboard.hpp and
+// root_tasks.hpp's fill-free solve_flips / solve_legal: the layout, the key, one
+// board's begin / apply / select / leaf / outputs, and the three calls for one
+// board (puct_begin_board, puct_advance_board, puct_result_board), which
+// tests/host/puct_host.cpp compiles with g++ and loops over the boards.
+//
+// Device mapping: one lane per board runs those three
+// functions.  Every word of a board's tree, header and leaf is read and written
+// by that one lane, so there is nothing to fence and no atomic; launches on a
+// stream order one simulation after another.  The observation of the leaves is
+// a second launch of the observation kernels on the workspace's leaf arrays.
+#pragma once
+#include <math.h>
+
+#include "mcts.hpp"
+
+#ifndef OTH_PUCT_SELECT_CHUNK
+// children whose words the selection loads ahead of their keys (1: a load per key)
+#define OTH_PUCT_SELECT_CHUNK 4
+#endif
+
+namespace oth {
+
+constexpr int PUCT_VALUE_ONE = 32768, PUCT_PRIOR_MAX = 65535, PUCT_MAX_C = 65535;
+constexpr int PUCT_MAX_TREE_NODES = 1 << 24, PUCT_MAX_SIMS = (1 << 24) - 1;
+constexpr int PUCT_LEAF_NONE = 0, PUCT_LEAF_EXPAND = 1, PUCT_LEAF_VALUE = 2, PUCT_LEAF_TERMINAL = 3;
+
+// floor(num / den) for num < 2^53, 0 < den < 2^53: both are exact in a double, the
+// double's quotient is within one of it, and an integer correction makes it
+// exact without a 64-bit division (mcts_key's way)
+OTH_HD uint64_t puct_floor_div(uint64_t num, uint64_t den) {
+    uint64_t q = (uint64_t)((double)num / (double)den);
+    if (q * den > num) --q;
+    else if ((q + 1) * den <= num) ++q;
+    return q;
+}
+
+// floor(w / v) toward minus infinity, |w| <= 2^15 v, 0 < v < 2^24
+OTH_HD int64_t puct_floor_q(int64_t w, uint32_t v) {
+    const uint64_t a = (uint64_t)(w < 0 ? -w : w);
+    const uint64_t q = puct_floor_div(a, (uint64_t)v);
+    if (w >= 0) return (int64_t)q;
+    return q * (uint64_t)v == a ? -(int64_t)q : -(int64_t)q - 1;
+}
+
+// cs = C isqrt(2^16 v_p) < 2^36; the key is q_c + floor(cs P_c / (2^17 (1 + v_c))), its numerator below 2^52
+OTH_HD int64_t puct_key(int64_t w_c, uint32_t v_c, uint32_t P_c, uint64_t cs) {
+    const int64_t q = v_c == 0 ? 0 : puct_floor_q(w_c, v_c);
+    return q + (int64_t)puct_floor_div(cs * (uint64_t)P_c, (uint64_t)(1u + v_c) << 17);
+}
+
+// the words of one node, of the workspace, and the tag of a search (n, E, T: what an advance must match)
+constexpr int puct_node_words(int n) { return 3 * ((n * n + 63) / 64) + 4; }
+constexpr uint64_t puct_ws_words(int n, uint64_t E, uint64_t T) {
+    return 2u + 2u * E + 3u * (uint64_t)((n * n + 63) / 64) * E + (E + 3u) / 4u + E * T * (uint64_t)puct_node_words(n);
+}
+OTH_HD uint64_t puct_tag(int n, uint32_t E, uint32_t T) {
+    return 0x7075637400000000ull ^ ((uint64_t)(uint32_t)n << 56) ^ ((uint64_t)T << 32) ^ (uint64_t)E;
+}
+
+template <int N>
+struct PuctWs {
+    static constexpr int W = Geo<N>::W;
+    uint64_t* base;
+    uint32_t E, T;
+    OTH_HD uint64_t* tag() const { return base; }
+    OTH_HD uint64_t* hdr(uint32_t e) const { return base + 2 + 2 * (size_t)e; }
+    OTH_HD uint64_t* leaf_boards() const { return base + 2 + 2 * (size_t)E; }
+    OTH_HD uint64_t* leaf_legal() const { return leaf_boards() + 2 * W * (size_t)E; }
+    OTH_HD uint16_t* leaf_meta() const { return reinterpret_cast<uint16_t*>(leaf_legal() + W * (size_t)E); }
+    OTH_HD uint64_t* tree(uint32_t e) const {
+        return leaf_legal() + W * (size_t)E + ((size_t)E + 3) / 4 + (size_t)e * T * (size_t)puct_node_words(N);
+    }
+};
+
+// the caller's leaf arrays of one call (oth_puct_leaves without the observation), each may be null
+struct PuctLeaves {
+    uint8_t* kind;
+    uint64_t* boards;
+    uint16_t* meta;
+    uint64_t* legal;
+};
+
+template <int N>
+struct PuctTree {
+    static constexpr int W = Geo<N>::W, NN = N * N;
+    static constexpr int WORDS = 3 * W + 4;
+    static constexpr int AT_W = 3 * W, AT_VP = 3 * W + 1, AT_LINK = 3 * W + 2, AT_INFO = 3 * W + 3;
+    static constexpr uint32_t F_TURN = 1u, F_MADE = 2u, F_TERM = 4u;
+
+    uint64_t* t;  // the board's T nodes
+    uint32_t used;
+
+    OTH_HD uint64_t* node(uint32_t i) const { return t + (size_t)i * WORDS; }
+
+    // the position of a made node: a position as oth_step with flags 0 leaves it (tw: white is to
+    // move; moves: the side to move's, none: terminated)
+    OTH_HD void put_position(uint32_t i, const BB<W>& black, const BB<W>& white, bool tw, const BB<W>& moves,
+                             uint32_t sq) const {
+        uint64_t* nd = node(i);
+#pragma unroll
+        for (int j = 0; j < W; ++j) {
+            nd[j] = black.w[j];
+            nd[W + j] = white.w[j];
+            nd[2 * W + j] = moves.w[j];
+        }
+        const uint32_t k = (uint32_t)popcount(moves);
+        nd[AT_INFO] = (uint64_t)k | (uint64_t)((tw ? F_TURN : 0u) | F_MADE | (k == 0 ? F_TERM : 0u) | sq << 8) << 32;
+    }
+
+    OTH_HD void put_root(const BB<W>& black, const BB<W>& white, bool tw, const BB<W>& moves) {
+        put_position(0, black, white, tw, moves, 0u);
+        uint64_t* nd = node(0);
+        nd[AT_W] = 0ull;
+        nd[AT_VP] = 0ull;
+        nd[AT_LINK] = 0ull;
+        used = 1u;
+    }
+
+    OTH_HD void position(uint32_t i, BB<W>& black, BB<W>& white, BB<W>& moves) const {
+        const uint64_t* nd = node(i);
+#pragma unroll
+        for (int j = 0; j < W; ++j) {
+            black.w[j] = nd[j];
+            white.w[j] = nd[W + j];
+            moves.w[j] = nd[2 * W + j];
+        }
+    }
+    OTH_HD uint32_t flags(uint32_t i) const { return (uint32_t)(node(i)[AT_INFO] >> 32); }
+
+    // the kind of a leaf without reserved children (the header's selection rule)
+    OTH_HD int leaf_kind(uint32_t i, uint32_t T) const {
+        const uint64_t info = node(i)[AT_INFO];
+        if ((uint32_t)(info >> 32) & F_TERM) return PUCT_LEAF_TERMINAL;
+        return (uint64_t)used + (uint32_t)info <= (uint64_t)T ? PUCT_LEAF_EXPAND : PUCT_LEAF_VALUE;
+    }
+
+    // Steps 1 to 3 of an advance: the value of leaf L for its side to move, its expansion, the backup.
+    // priors: the board's N*N, read at the leaf's moves only.
+    OTH_HD void apply(uint32_t L, int kind, uint32_t T, const int32_t* priors, int32_t value) {
+        uint64_t* nd = node(L);
+        BB<W> B, Wt, moves;
+        position(L, B, Wt, moves);
+        const bool s = (flags(L) & F_TURN) != 0;
+        int64_t val;
+        if (kind == PUCT_LEAF_TERMINAL) {
+            const int d = popcount(B) - popcount(Wt);  // black - white
+            val = (int64_t)PUCT_VALUE_ONE * sign_i32(s ? -d : d);
+        } else {
+            val = value < -PUCT_VALUE_ONE ? -PUCT_VALUE_ONE : (value > PUCT_VALUE_ONE ? PUCT_VALUE_ONE : value);
+        }
+        const uint32_t k = (uint32_t)nd[AT_INFO];
+        if (kind == PUCT_LEAF_EXPAND && (uint32_t)nd[AT_LINK] == 0u && (uint64_t)used + k <= (uint64_t)T) {
+            const uint32_t first = used;
+            used += k;
+            nd[AT_LINK] |= (uint64_t)first;
+            BB<W> rem = moves;
+            for (uint32_t j = 0; j < k; ++j) {  // ascending squares
+                const int a = lowest_square<W>(rem);
+                rem = rem & ~square<W>(a);
+                const int32_t pr = priors[a];
+                const uint32_t P = (uint32_t)(pr < 0 ? 0 : (pr > PUCT_PRIOR_MAX ? PUCT_PRIOR_MAX : pr));
+                uint64_t* ch = node(first + j);
+                ch[AT_W] = 0ull;
+                ch[AT_VP] = (uint64_t)P << 32;
+                ch[AT_LINK] = (uint64_t)L << 32;
+                ch[AT_INFO] = (uint64_t)((uint32_t)a << 8) << 32;
+            }
+        }
+        uint32_t cur = L;
+        while (cur != 0) {
+            uint64_t* c = node(cur);
+            const uint32_t parent = (uint32_t)(c[AT_LINK] >> 32);
+            const bool ptw = (flags(parent) & F_TURN) != 0;
+            c[AT_W] = (uint64_t)((int64_t)c[AT_W] + (ptw == s ? val : -val));
+            c[AT_VP] += 1ull;
+            cur = parent;
+        }
+        node(0)[AT_VP] += 1ull;
+    }
+
+    // child c of cur, reserved and not yet made: oth_step's ply with flags 0 on its square, a pass resolved
+    OTH_HD void make(uint32_t cur, uint32_t c) const {
+        BB<W> B, Wt, mv;
+        position(cur, B, Wt, mv);
+        const bool tw = (flags(cur) & F_TURN) != 0;
+        const uint32_t sq = flags(c) >> 8;
+        const int a = (int)sq;
+        const BB<W> bit = square<W>(a);
+        const BB<W> M = pick(tw, Wt, B), O = pick(tw, B, Wt);
+        const BB<W> fl = solve_flips<N>(M, O, a);
+        const BB<W> Mn = M | fl | bit, On = O & ~fl;
+        BB<W> Lg = solve_legal<N>(On, Mn);
+        const bool pass = !any(Lg);  // the reply is a pass: the same colour moves again, or the game is over
+        if (pass) Lg = solve_legal<N>(Mn, On);
+        put_position(c, pick(tw, On, Mn), pick(tw, Mn, On), pass ? tw : !tw, Lg, sq);
+    }
+
+    // Step 4: the descent from the root to the next leaf (made on the way if need be)
+    OTH_HD uint32_t select(uint32_t T, int C, int& kind) const {
+        uint32_t cur = 0;
+        kind = PUCT_LEAF_VALUE;  // (the level bound is never met: a level places a disc)
+        for (int level = 0; level < NN + 2; ++level) {
+            const uint64_t* nd = node(cur);
+            const uint32_t first = (uint32_t)nd[AT_LINK];
+            if ((flags(cur) & F_TERM) || first == 0u) {
+                kind = leaf_kind(cur, T);
+                break;
+            }
+            const uint32_t k = (uint32_t)nd[AT_INFO];
+            const uint64_t cs = (uint64_t)(uint32_t)C * mcts_isqrt((uint64_t)(uint32_t)nd[AT_VP] << 16);
+            int64_t bk = 0;
+            uint32_t bi = first;
+            // ascending squares: the first of equal keys is the lowest.  The children's words are
+            // loaded OTH_PUCT_SELECT_CHUNK children at a time ahead of their keys, so a lane waits
+            // for memory once per chunk and not once per child (a lane past k re-reads child k - 1).
+            for (uint32_t j0 = 0; j0 < k; j0 += OTH_PUCT_SELECT_CHUNK) {
+                uint64_t vp[OTH_PUCT_SELECT_CHUNK], cw[OTH_PUCT_SELECT_CHUNK];
+#pragma unroll
+                for (uint32_t u = 0; u < OTH_PUCT_SELECT_CHUNK; ++u) {
+                    const uint64_t* ch = node(first + (j0 + u < k ? j0 + u : k - 1u));
+                    vp[u] = ch[AT_VP];
+                    cw[u] = ch[AT_W];
+                }
+#pragma unroll
+                for (uint32_t u = 0; u < OTH_PUCT_SELECT_CHUNK; ++u) {
+                    const uint32_t j = j0 + u;
+                    const int64_t key = puct_key((int64_t)cw[u], (uint32_t)vp[u], (uint32_t)(vp[u] >> 32), cs);
+                    if (j < k && (j == 0 || key > bk)) {
+                        bk = key;
+                        bi = first + j;
+                    }
+                }
+            }
+            if (!(flags(bi) & F_MADE)) {
+                make(cur, bi);
+                cur = bi;
+                kind = leaf_kind(cur, T);
+                break;
+            }
+            cur = bi;
+        }
+        return cur;
+    }
+
+    // node i as a leaf in exchange format: turn, terminated and winner bits as oth_step sets them
+    OTH_HD void leaf(uint32_t i, BB<W>& black, BB<W>& white, BB<W>& moves, uint32_t& meta) const {
+        position(i, black, white, moves);
+        const uint32_t f = flags(i);
+        meta = f & F_TURN;
+        if (f & F_TERM) {
+            const int d = popcount(white) - popcount(black);
+            meta |= 2u | (d > 0 ? 1u : (d < 0 ? 2u : 0u)) << 2;
+        }
+    }
+
+    // The outputs of a searched board: the root's children by square, the best of them
+    OTH_HD void outputs(int32_t* visits, int64_t* value_sums, int32_t* best) const {
+        for (int a = 0; a < NN; ++a) {
+            visits[a] = 0;
+            if (value_sums) value_sums[a] = 0;
+        }
+        const uint64_t* root = node(0);
+        const uint32_t first = (uint32_t)root[AT_LINK], k = first ? (uint32_t)root[AT_INFO] : 0u;
+        uint32_t bv = 0;
+        int64_t bw = 0;
+        int ba = -1;
+        for (uint32_t j = 0; j < k; ++j) {
+            const uint64_t* ch = node(first + j);
+            const uint32_t v = (uint32_t)ch[AT_VP];
+            const int64_t w = (int64_t)ch[AT_W];
+            const int a = (int)(flags(first + j) >> 8);
+            visits[a] = (int32_t)v;
+            if (value_sums) value_sums[a] = w;
+            if (v > 0 && (ba < 0 || v > bv || (v == bv && w > bw))) {  // (no best while no child has a visit)
+                ba = a;
+                bv = v;
+                bw = w;
+            }
+        }
+        if (best) *best = ba;
+    }
+};
+
+// The leaf arrays of board e after a call: the pending leaf, or (kind NONE) the root with the meta
+// the handle held at begin; into the workspace's arrays and the caller's.
+template <int N>
+OTH_HD void puct_write_leaf(const PuctWs<N>& ws, uint32_t e, const PuctTree<N>& tr, uint32_t L, int kind,
+                            uint32_t root_meta, const PuctLeaves& out) {
+    constexpr int W = Geo<N>::W;
+    BB<W> B, Wt, Lg;
+    uint32_t meta;
+    if (kind == PUCT_LEAF_NONE) {
+        tr.position(0, B, Wt, Lg);
+        meta = root_meta;
+    } else {
+        tr.leaf(L, B, Wt, Lg, meta);
+    }
+    uint64_t* lb = ws.leaf_boards() + (size_t)e * 2 * W;
+    uint64_t* ll = ws.leaf_legal() + (size_t)e * W;
+#pragma unroll
+    for (int j = 0; j < W; ++j) {
+        lb[j] = B.w[j];
+        lb[W + j] = Wt.w[j];
+        ll[j] = Lg.w[j];
+        if (out.boards) {
+            out.boards[(size_t)e * 2 * W + j] = B.w[j];
+            out.boards[(size_t)e * 2 * W + W + j] = Wt.w[j];
+        }
+        if (out.legal) out.legal[(size_t)e * W + j] = Lg.w[j];
+    }
+    ws.leaf_meta()[e] = (uint16_t)meta;
+    if (out.meta) out.meta[e] = (uint16_t)meta;
+    if (out.kind) out.kind[e] = (uint8_t)kind;
+}
+
+// oth_puct_begin for board e (the handle's black, white, stored possible_moves and meta)
+template <int N>
+OTH_HD void puct_begin_board(const PuctWs<N>& ws, uint32_t e, const uint64_t* black, const uint64_t* white,
+                             const uint64_t* stored, uint32_t meta, const PuctLeaves& out) {
+    constexpr int W = Geo<N>::W;
+    BB<W> B, Wt, Lg;
+#pragma unroll
+    for (int i = 0; i < W; ++i) {
+        B.w[i] = black[i];
+        Wt.w[i] = white[i];
+        Lg.w[i] = stored[i];
+    }
+    const int st = mcts_status<N>(Lg, meta);
+    PuctTree<N> tr{ws.tree(e), 1u};
+    tr.put_root(B, Wt, (meta & 1u) != 0, Lg & Geo<N>::BOARD);
+    // (a stored mask of more than T - 1 squares, which no position of the game has, makes the root a VALUE leaf)
+    const int kind = st == MCTS_DONE ? tr.leaf_kind(0, ws.T) : PUCT_LEAF_NONE;
+    uint64_t* h = ws.hdr(e);
+    h[0] = 1ull;  // used = 1, the pending leaf is the root
+    h[1] = (uint64_t)(uint32_t)kind | (uint64_t)(uint32_t)st << 8 | (uint64_t)(meta & 0xffffu) << 32;
+    puct_write_leaf<N>(ws, e, tr, 0u, kind, meta & 0xffffu, out);
+}
+
+// oth_puct_advance for board e.  priors: the board's N*N; the workspace is one that puct_begin_board wrote.
+template <int N>
+OTH_HD void puct_advance_board(const PuctWs<N>& ws, uint32_t e, int C, const int32_t* priors, int32_t value,
+                               bool more, const PuctLeaves& out) {
+    uint64_t* h = ws.hdr(e);
+    const uint64_t h0 = h[0], h1 = h[1];
+    PuctTree<N> tr{ws.tree(e), (uint32_t)h0};
+    uint32_t L = (uint32_t)(h0 >> 32);
+    int kind = (int)(h1 & 0xffu);
+    if (tr.used > ws.T || L >= ws.T) kind = PUCT_LEAF_NONE, L = 0u;  // (a header no begin wrote: nothing is followed)
+    if (kind != PUCT_LEAF_NONE) {
+        tr.apply(L, kind, ws.T, priors, value);
+        kind = PUCT_LEAF_NONE;
+        L = 0u;
+        if (more && (uint32_t)tr.node(0)[PuctTree<N>::AT_VP] < (uint32_t)PUCT_MAX_SIMS) L = tr.select(ws.T, C, kind);
+        h[0] = (uint64_t)tr.used | (uint64_t)L << 32;
+        h[1] = (h1 & ~0xffull) | (uint64_t)(uint32_t)kind;
+    }
+    puct_write_leaf<N>(ws, e, tr, L, kind, (uint32_t)(h1 >> 32), out);
+}
+
+// oth_puct_result for board e.  visits / value_sums: the board's N*N; value_sums, best, tree_nodes, status may be null.
+template <int N>
+OTH_HD void puct_result_board(const PuctWs<N>& ws, uint32_t e, int32_t* visits, int64_t* value_sums, int32_t* best,
+                              int32_t* tree_nodes, uint8_t* status) {
+    constexpr int NN = N * N;
+    const uint64_t* h = ws.hdr(e);
+    const uint32_t used = (uint32_t)h[0];
+    const int st = (int)((h[1] >> 8) & 0xffu);
+    if (status) *status = (uint8_t)st;
+    if (st != MCTS_DONE || used > ws.T) {
+        for (int a = 0; a < NN; ++a) {
+            visits[a] = 0;
+            if (value_sums) value_sums[a] = 0;
+        }
+        if (best) *best = -1;
+        if (tree_nodes) *tree_nodes = 1;
+        return;
+    }
+    const PuctTree<N> tr{ws.tree(e), used};
+    tr.outputs(visits, value_sums, best);
+    if (tree_nodes) *tree_nodes = (int32_t)used;
+}
+
+}  // namespace oth
+
+#if defined(__HIPCC__)
+#include "state.hpp"
+
+namespace oth_dev {
+
+static_assert(PUCT_VALUE_ONE == OTH_PUCT_VALUE_ONE && PUCT_PRIOR_MAX == OTH_PUCT_PRIOR_MAX &&
+                  PUCT_MAX_C == OTH_PUCT_MAX_C && PUCT_MAX_TREE_NODES == OTH_PUCT_MAX_TREE_NODES &&
+                  PUCT_MAX_SIMS == OTH_PUCT_MAX_SIMS,
+              "the header's limits");
+static_assert(PUCT_LEAF_NONE == OTH_PUCT_LEAF_NONE && PUCT_LEAF_EXPAND == OTH_PUCT_LEAF_EXPAND &&
+                  PUCT_LEAF_VALUE == OTH_PUCT_LEAF_VALUE && PUCT_LEAF_TERMINAL == OTH_PUCT_LEAF_TERMINAL,
+              "the header's leaf kinds");
+
+constexpr int PUCT_BLOCK = 64;  // one wave a block, one lane a board
+
+template <int N>
+__global__ __launch_bounds__(PUCT_BLOCK) void k_puct_begin(const uint64_t* __restrict__ boards,
+                                                           const uint16_t* __restrict__ meta,
+                                                           const uint64_t* __restrict__ legal, int E, uint32_t T,
+                                                           uint64_t* __restrict__ wsp, PuctLeaves out) {
+    constexpr int W = Geo<N>::W;
+    const long long e = (long long)blockIdx.x * PUCT_BLOCK + threadIdx.x;
+    const PuctWs<N> ws{wsp, (uint32_t)E, T};
+    if (e == 0) *ws.tag() = puct_tag(N, (uint32_t)E, T);
+    if (e >= E) return;
+    puct_begin_board<N>(ws, (uint32_t)e, boards + (size_t)e * 2 * W, boards + (size_t)e * 2 * W + W,
+                        legal + (size_t)e * W, meta[e], out);
+}
+
+// (a workspace whose tag is not this search's -- no begin for this handle and T -- is left alone)
+template <int N>
+__global__ __launch_bounds__(PUCT_BLOCK) void k_puct_advance(int E, uint32_t T, int C, uint64_t* __restrict__ wsp,
+                                                             const int32_t* __restrict__ priors,
+                                                             const int32_t* __restrict__ values, int more,
+                                                             PuctLeaves out) {
+    const long long e = (long long)blockIdx.x * PUCT_BLOCK + threadIdx.x;
+    const PuctWs<N> ws{wsp, (uint32_t)E, T};
+    if (e >= E || *ws.tag() != puct_tag(N, (uint32_t)E, T)) return;
+    puct_advance_board<N>(ws, (uint32_t)e, C, priors + (size_t)e * (N * N), values[e], more != 0, out);
+}
+
+template <int N>
+__global__ __launch_bounds__(PUCT_BLOCK) void k_puct_result(int E, uint32_t T, uint64_t* __restrict__ wsp,
+                                                            int32_t* __restrict__ visits,
+                                                            int64_t* __restrict__ value_sums,
+                                                            int32_t* __restrict__ best,
+                                                            int32_t* __restrict__ tree_nodes,
+                                                            uint8_t* __restrict__ status) {
+    constexpr int NN = N * N;
+    const long long e = (long long)blockIdx.x * PUCT_BLOCK + threadIdx.x;
+    const PuctWs<N> ws{wsp, (uint32_t)E, T};
+    if (e >= E || *ws.tag() != puct_tag(N, (uint32_t)E, T)) return;
+    puct_result_board<N>(ws, (uint32_t)e, visits + (size_t)e * NN, value_sums ? value_sums + (size_t)e * NN : nullptr,
+                         best ? best + e : nullptr, tree_nodes ? tree_nodes + e : nullptr,
+                         status ? status + e : nullptr);
+}
+
+}  // namespace oth_dev
+#endif

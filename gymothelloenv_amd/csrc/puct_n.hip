@@ -1,0 +1,79 @@
+// puct_n.hip -- k_puct_begin, k_puct_advance, k_puct_result (oth_puct_begin /
+// _advance / _result: a tree search per board whose leaves are evaluated between
+// launches, puct.hpp) in a translation unit of its own per board size
+// (-DOTH_N=4 .. 16), like mcts_n.hip.
+#include "puct.hpp"
+#include "launch.hpp"
+
+#ifndef OTH_N
+#error "compile with -DOTH_N=<board size>"
+#endif
+
+using namespace oth;
+using namespace oth_dev;
+
+namespace oth_host {
+
+static_assert(puct_ws_words(OTH_N, 1, OTH_N * OTH_N) == puct_workspace_words(OTH_N, 1, OTH_N * OTH_N) &&
+                  puct_ws_words(OTH_N, 70, 4096) == puct_workspace_words(OTH_N, 70, 4096) &&
+                  puct_ws_words(OTH_N, 65536, 1 << 24) == puct_workspace_words(OTH_N, 65536, 1 << 24),
+              "oth_puct_workspace_bytes' layout");
+static_assert(PuctTree<OTH_N>::WORDS == puct_node_words(OTH_N), "the node size");
+
+namespace {
+
+unsigned puct_grid(int E) { return (unsigned)(((long long)E + PUCT_BLOCK - 1) / PUCT_BLOCK); }
+
+// the observation of the leaves: the observation kernels on the workspace's leaf arrays
+template <int N>
+int puct_observe(oth_env* env, const PuctWs<N>& ws, const oth_puct_leaves* lv, const char* what, hipStream_t st) {
+    if (int rc = after_launch(what)) return rc;
+    if (!lv || !lv->obs) return OTH_OK;
+    oth_env view = *env;  // launch_observe reads the geometry and these three pointers
+    view.boards = ws.leaf_boards();
+    view.meta = ws.leaf_meta();
+    view.legal = ws.leaf_legal();
+    return launch_observe<N>(&view, lv->layout, lv->dtype, lv->obs, st);
+}
+
+PuctLeaves leaves_of(const oth_puct_leaves* lv) {
+    if (!lv) return PuctLeaves{nullptr, nullptr, nullptr, nullptr};
+    return PuctLeaves{lv->kind, lv->boards, lv->meta, lv->legal};
+}
+
+}  // namespace
+
+template <int N>
+int launch_puct_begin(oth_env* env, const oth_puct_params* p, void* workspace, const oth_puct_leaves* lv,
+                      hipStream_t st) {
+    const PuctWs<N> ws{reinterpret_cast<uint64_t*>(workspace), (uint32_t)env->E, (uint32_t)p->max_tree_nodes};
+    launch_k(k_puct_begin<N>, dim3(puct_grid(env->E)), dim3(PUCT_BLOCK), 0, st, env->boards, env->meta, env->legal,
+             env->E, ws.T, ws.base, leaves_of(lv));
+    return puct_observe<N>(env, ws, lv, "oth_puct_begin", st);
+}
+
+template <int N>
+int launch_puct_advance(oth_env* env, const oth_puct_params* p, void* workspace, const int32_t* priors,
+                        const int32_t* values, int more, const oth_puct_leaves* lv, hipStream_t st) {
+    const PuctWs<N> ws{reinterpret_cast<uint64_t*>(workspace), (uint32_t)env->E, (uint32_t)p->max_tree_nodes};
+    launch_k(k_puct_advance<N>, dim3(puct_grid(env->E)), dim3(PUCT_BLOCK), 0, st, env->E, ws.T, p->c_puct, ws.base,
+             priors, values, more, leaves_of(lv));
+    return puct_observe<N>(env, ws, lv, "oth_puct_advance", st);
+}
+
+template <int N>
+int launch_puct_result(oth_env* env, const oth_puct_params* p, void* workspace, int32_t* visits, int64_t* value_sums,
+                       int32_t* best, int32_t* tree_nodes, uint8_t* status, hipStream_t st) {
+    launch_k(k_puct_result<N>, dim3(puct_grid(env->E)), dim3(PUCT_BLOCK), 0, st, env->E,
+             (uint32_t)p->max_tree_nodes, reinterpret_cast<uint64_t*>(workspace), visits, value_sums, best, tree_nodes,
+             status);
+    return after_launch("oth_puct_result");
+}
+
+template int launch_puct_begin<OTH_N>(oth_env*, const oth_puct_params*, void*, const oth_puct_leaves*, hipStream_t);
+template int launch_puct_advance<OTH_N>(oth_env*, const oth_puct_params*, void*, const int32_t*, const int32_t*, int,
+                                        const oth_puct_leaves*, hipStream_t);
+template int launch_puct_result<OTH_N>(oth_env*, const oth_puct_params*, void*, int32_t*, int64_t*, int32_t*, int32_t*,
+                                       uint8_t*, hipStream_t);
+
+}  // namespace oth_host

@@ -188,6 +188,49 @@ class MCTSPolicy(object):
         return self.get_action(obs)
 
 
+class PUCTPolicy(object):
+    """Network-guided tree search move selection (no reference counterpart: the
+    rung after MCTSPolicy): the most visited root move of `simulations` simulations
+    of VecOthelloEnv.puct_search, whose leaves `evaluate(leaves) -> (logits, values)`
+    judges -- a policy and value network, or one of the evaluators that need none
+    (None: playout_evaluator(8, seed), which replays its games move for move).  c is
+    the exploration constant; simulations >= 2 (the first evaluates the root alone)."""
+
+    def __init__(self, evaluate=None, simulations=128, c=1.25, seed=0):
+        self.env = None
+        self.simulations, self.c = int(simulations), float(c)
+        self._seed = int(seed)
+        self._own = evaluate is None
+        self.evaluate = evaluate
+        self.counter = 0
+        if self.simulations < 2:
+            raise ValueError("simulations must be >= 2: the first evaluates the root alone")
+
+    def reset(self, env):
+        self.env = _base(env)
+
+    def seed(self, seed):
+        self._seed = int(seed)
+        self.counter = 0
+        if self._own:
+            self.evaluate = None
+
+    def get_action(self, obs):
+        vec = self.env._vec
+        self.env._sync()
+        if self.evaluate is None:
+            from .vec_env import playout_evaluator
+            self.evaluate = playout_evaluator(8, seed=self._seed)
+        a = int(vec.puct_actions(self.evaluate, self.simulations, c=self.c).cpu()[0])
+        self.counter += 1
+        if a < 0:
+            raise ValueError('no possible moves')
+        return a
+
+    def get_test_action(self, obs):
+        return self.get_action(obs)
+
+
 class SolverPolicy(object):
     """Perfect endgame play (no reference counterpart): once the board has at most
     max_empties empty squares the move is the exact solver's `best` (oth_solve: the
@@ -257,4 +300,4 @@ class SearchPolicy(object):
         return self.get_action(obs)
 
 
-__all__ = ['RandomPolicy', 'GreedyPolicy', 'MaxiMinPolicy', 'MonteCarloPolicy', 'MCTSPolicy', 'SolverPolicy', 'SearchPolicy', 'PROTAGONIST_TURN', 'OPPONENT_TURN', 'WHITE_DISK']
+__all__ = ['RandomPolicy', 'GreedyPolicy', 'MaxiMinPolicy', 'MonteCarloPolicy', 'MCTSPolicy', 'PUCTPolicy', 'SolverPolicy', 'SearchPolicy', 'PROTAGONIST_TURN', 'OPPONENT_TURN', 'WHITE_DISK']

@@ -7,6 +7,7 @@ that stay on the device.  It replaces the reference's CPU "vector env" of one
 process per board (envs.py:7-287) for the hot path; torch here is only device
 memory, streams and the collective for the W/D/L tally.
 """
+import collections
 import contextlib
 import ctypes
 
@@ -41,6 +42,73 @@ def nwords(n):
 
 def _ptr(t):
     return None if t is None else ctypes.c_void_p(t.data_ptr())
+
+
+# the leaves of a network-guided search (VecOthelloEnv.puct_begin / puct_advance)
+PuctLeaves = collections.namedtuple("PuctLeaves", ("kind", "boards", "meta", "legal", "obs"))
+
+
+def puct_quantize(logits, leaf_legal, values):
+    """The integers oth_puct_advance takes, from a network's floats: priors int32
+    (E, N*N) = round(65535 p), p the softmax of `logits` (E, N*N) over the leaf's
+    legal squares (`leaf_legal`: PuctLeaves.legal, int64 (E, W)) in float32 on the
+    device, 0 elsewhere (and on a leaf without a legal square); values int32 (E,) =
+    round(32768 clamp(v, -1, 1)), v the value for the leaf's side to move.
+
+    This is the only place of the search where floats appear: the search is exact
+    *given* these integers, which is what its tests pin; how a network's floats
+    round is the caller's business."""
+    E = logits.shape[0]
+    lg = logits.reshape(E, -1).to(torch.float32)
+    nn = lg.shape[1]
+    a = torch.arange(nn, device=lg.device)
+    mask = ((leaf_legal.to(lg.device).view(E, -1)[:, a // 64] >> (a % 64)) & 1).bool()
+    p = torch.softmax(lg.masked_fill(~mask, float("-inf")), dim=1)
+    p = torch.where(mask, p, torch.zeros_like(p))  # (a row without a legal square: nan -> 0)
+    priors = torch.round(p * float(L.OTH_PUCT_PRIOR_MAX)).to(torch.int32)
+    v = values.reshape(E).to(device=lg.device, dtype=torch.float32).clamp(-1.0, 1.0)
+    return priors, torch.round(v * float(L.OTH_PUCT_VALUE_ONE)).to(torch.int32)
+
+
+def _leaves_board_size(leaves):
+    if leaves.obs is None:
+        raise ValueError("this evaluator takes the board size from leaves.obs: begin the search with a layout")
+    return int(leaves.obs.shape[-1])
+
+
+def uniform_evaluator(leaves):
+    """The evaluator that knows nothing: zero logits (a uniform prior over the legal
+    squares) and value 0.  With it the search is a breadth-first tree whose only
+    values are the game ends it reaches."""
+    n, E = _leaves_board_size(leaves), leaves.kind.shape[0]
+    dev = leaves.kind.device
+    return torch.zeros(E, n * n, device=dev), torch.zeros(E, device=dev)
+
+
+class playout_evaluator(object):
+    """An evaluator without a network: the value of a leaf is (wins - losses) / R of
+    R random games from it, played on the device by a private second VecOthelloEnv
+    that is loaded with the leaves (set_state) -- the leaf evaluation of mcts(),
+    through the evaluator interface; the logits are zero.  It shows how an
+    evaluator plugs in; a learner puts its network here.  Playouts are keyed by
+    `seed` and a call counter, so a search repeats."""
+
+    def __init__(self, n_playouts=8, seed=0):
+        self.n_playouts, self.seed, self.counter = int(n_playouts), int(seed), 0
+        self._env = None
+
+    def __call__(self, leaves):
+        n, E = _leaves_board_size(leaves), leaves.kind.shape[0]
+        env = self._env
+        if env is None or env.num_envs != E or env.board_size != n or env.device != leaves.kind.device:
+            if env is not None:
+                env.close()
+            env = self._env = VecOthelloEnv(E, board_size=n, device=leaves.kind.device)
+        env.set_state(leaves.boards, leaves.meta, leaves.legal)
+        wdl = env.playouts(self.n_playouts, seed=self.seed, counter=self.counter)
+        self.counter += 1
+        values = (wdl[:, 0] - wdl[:, 2]).to(torch.float32) / float(self.n_playouts)
+        return torch.zeros(E, n * n, device=values.device), values
 
 
 class VecOthelloEnv(object):
@@ -91,6 +159,8 @@ class VecOthelloEnv(object):
         self._sample_calls = 0  # Philox counter of sample_actions
         self._playout_calls = 0  # `counter` of the next playouts() call that gives none
         self._mcts_ws = None  # mcts()'s workspace: a uint8 tensor, regrown only when too small
+        self._puct_ws = None  # the puct_* search's workspace, its own: mcts() would overwrite a search in progress
+        self._puct = None  # the search in progress: (params, the C leaves struct, PuctLeaves)
         self._region_resets = None  # resets inside an open graph region (None: no region)
 
     # ------------------------------------------------------------------ utils
@@ -586,6 +656,139 @@ class VecOthelloEnv(object):
         for k in ("wins2", "best", "tree_nodes", "status"):
             kw.pop(k, None)
         return self.mcts(iterations, best=True, **kw)[1]
+
+    # ------------------------------------------------ network-guided tree search
+    def puct_begin(self, c=1.25, max_tree_nodes=None, layout="make_state", dtype=torch.float32):
+        """Begin a network-guided tree search from every board's position
+        (oth_puct_begin; include/othello_mi355x.h defines every step in integers):
+        exploration constant c (round(256 c) in the key), max_tree_nodes node slots
+        per board (None: max(N*N, 64 (N*N - 4)), what 256 simulations can reserve at
+        most).  Returns the leaves to evaluate, a PuctLeaves of tensors on this device:
+          kind   uint8 (E,): OTH_PUCT_LEAF_EXPAND (priors and value wanted), VALUE
+                 (value only), TERMINAL (nothing), NONE (the board has no pending leaf);
+          boards int64 (E, 2W), meta int16 (E,), legal int64 (E, W): the leaves in
+                 the exchange format of get_state / set_state (a board without a
+                 pending leaf shows its root, so every row is a valid input);
+          obs    observe(layout, dtype) of those positions (layout=None: none).
+        These tensors belong to the search: every puct_advance writes the next
+        leaves into them in place (so a captured advance keeps feeding the same
+        network input), and the next puct_begin makes new ones.  The boards, the
+        ply counter and the tallies are left untouched.  The tree lives in a cached
+        workspace of its own (not mcts()'s, whose call would overwrite a search in
+        progress), regrown only when too small."""
+        E, nn = self.num_envs, self.board_size * self.board_size
+        if max_tree_nodes is None:
+            max_tree_nodes = min(max(nn, 64 * (nn - 4)), L.OTH_PUCT_MAX_TREE_NODES)
+        cx = int(round(256 * float(c)))
+        for name, v in (("c", cx), ("max_tree_nodes", int(max_tree_nodes))):
+            if not -2 ** 31 <= v < 2 ** 31:
+                raise ValueError("%s is out of range" % name)
+        p = L.OthPuctParams(cx, int(max_tree_nodes))
+        obs = None
+        lay = 0
+        if layout is not None:
+            lay = _OBS_LAYOUTS.get(layout, -1) if isinstance(layout, str) else int(layout)
+            if lay not in _OBS_PLANES or dtype not in _DTYPES:
+                raise ValueError("unknown observation layout %r or dtype %r" % (layout, dtype))
+            obs = torch.empty(self._obs_shape(lay), dtype=dtype, device=self.device)
+        need = ctypes.c_uint64(0)
+        L.check(self._lib.oth_puct_workspace_bytes(self.board_size, E, p.max_tree_nodes, ctypes.byref(need)),
+                "oth_puct_workspace_bytes")
+        if self._puct_ws is None or self._puct_ws.numel() < need.value:
+            self._puct_ws = None  # (the old one goes first)
+            self._puct_ws = torch.empty(need.value, dtype=torch.uint8, device=self.device)
+        leaves = PuctLeaves(self._u8(E), torch.empty(E, 2 * self.words, dtype=torch.int64, device=self.device),
+                            torch.empty(E, dtype=torch.int16, device=self.device),
+                            torch.empty(E, self.words, dtype=torch.int64, device=self.device), obs)
+        lv = L.OthPuctLeaves(leaves.kind.data_ptr(), leaves.boards.data_ptr(), leaves.meta.data_ptr(),
+                             leaves.legal.data_ptr(), None if obs is None else obs.data_ptr(), lay,
+                             _DTYPES[dtype] if obs is not None else 0)
+        self._puct = None
+        L.check(self._lib.oth_puct_begin(self._h, ctypes.byref(p), _ptr(self._puct_ws), self._puct_ws.numel(),
+                                         ctypes.byref(lv), self._stream()), "oth_puct_begin")
+        self._puct = (p, lv, leaves)
+        return leaves
+
+    def _puct_state(self):
+        if self._puct is None:
+            raise RuntimeError("no search in progress: call puct_begin() first")
+        return self._puct
+
+    def puct_advance(self, priors, values, more=True):
+        """One simulation of every board's search (oth_puct_advance): the pending
+        leaves take their evaluation -- priors int32 (E, N*N) in [0, 65535] (read at
+        the leaf's legal squares only; 65535 is probability 1), values int32 (E,) in
+        [-32768, 32768] for the leaf's side to move, both as puct_quantize makes
+        them -- are expanded and backed up, and, unless more is false, each search
+        descends to its next leaf.  Returns puct_begin's PuctLeaves, rewritten in
+        place.  int32 tensors on this device are passed as they are (a captured
+        advance reads them again at every replay); others are converted first."""
+        p, lv, leaves = self._puct_state()
+        E, nn = self.num_envs, self.board_size * self.board_size
+        pr = priors.to(device=self.device, dtype=torch.int32).contiguous()
+        vl = values.to(device=self.device, dtype=torch.int32).contiguous()
+        if pr.numel() != E * nn or vl.numel() != E:
+            raise ValueError("priors must have %d elements and values %d" % (E * nn, E))
+        L.check(self._lib.oth_puct_advance(self._h, ctypes.byref(p), _ptr(self._puct_ws), self._puct_ws.numel(),
+                                           _ptr(pr), _ptr(vl), int(bool(more)), ctypes.byref(lv), self._stream()),
+                "oth_puct_advance")
+        return leaves
+
+    def puct_result(self, value_sums=False, best=False, tree_nodes=False, status=False):
+        """The search's outputs so far (oth_puct_result; it may be called at any point
+        and changes nothing): visits, then value_sums, best, tree_nodes and status when
+        asked (the header's order), as tensors on this device:
+          visits     int32 (E, N*N): the simulations through the root's child on each
+                     square, 0 without a child -- the visit-count policy target;
+          value_sums int64 (E, N*N): the sum of the values backed up through it, in
+                     units of 2^-15, for the side to move at the root;
+          best       int32 (E,): the most visited child (then the larger value sum,
+                     then the lowest square), -1 while no child has a visit;
+          tree_nodes int32 (E,): node slots the board's tree used;
+          status     uint8 (E,): OTH_MCTS_DONE / TERMINATED / NO_MOVE."""
+        p, lv, leaves = self._puct_state()
+        E, nn = self.num_envs, self.board_size * self.board_size
+        vis = self._i32(E, nn)
+        vs = torch.empty(E, nn, dtype=torch.int64, device=self.device) if value_sums else None
+        bt = self._i32(E) if best else None
+        tn = self._i32(E) if tree_nodes else None
+        stt = self._u8(E) if status else None
+        L.check(self._lib.oth_puct_result(self._h, ctypes.byref(p), _ptr(self._puct_ws), self._puct_ws.numel(),
+                                          _ptr(vis), _ptr(vs), _ptr(bt), _ptr(tn), _ptr(stt), self._stream()),
+                "oth_puct_result")
+        res = (vis,) + tuple(t for t in (vs, bt, tn, stt) if t is not None)
+        return res[0] if len(res) == 1 else res
+
+    def puct_search(self, evaluate, simulations, **kw):
+        """The whole loop: puct_begin, then `simulations` times evaluate(leaves) ->
+        (logits (E, N*N), values (E,)) -- any callable, a torch module's forward on
+        leaves.obs for example -- quantised by puct_quantize and given to
+        puct_advance (more=False on the last), then puct_result.  c,
+        max_tree_nodes (None: what `simulations` can reserve at most), layout and
+        dtype go to puct_begin, value_sums / best / tree_nodes / status to
+        puct_result, whose outputs are returned.  evaluate's floats are the only ones
+        anywhere: given the integers puct_quantize makes of them, the search is exact."""
+        S = int(simulations)
+        if S < 1:
+            raise ValueError("simulations must be >= 1")
+        begin = dict((k, kw.pop(k)) for k in ("c", "max_tree_nodes", "layout", "dtype") if k in kw)
+        if begin.get("max_tree_nodes") is None:
+            nn = self.board_size * self.board_size
+            begin["max_tree_nodes"] = min(max(nn, S * (nn - 4) // 4 + nn), L.OTH_PUCT_MAX_TREE_NODES)
+        leaves = self.puct_begin(**begin)
+        for i in range(S):
+            logits, values = evaluate(leaves)
+            priors, vals = puct_quantize(logits, leaves.legal, values)
+            leaves = self.puct_advance(priors, vals, more=i < S - 1)
+        return self.puct_result(**kw)
+
+    def puct_actions(self, evaluate, simulations, **kw):
+        """Every board's most visited root move of puct_search(evaluate, simulations,
+        **kw) (its `best`): int32 (E,), -1 for a board without a possible move (or
+        with simulations = 1, which evaluates the root alone)."""
+        for k in ("value_sums", "best", "tree_nodes", "status"):
+            kw.pop(k, None)
+        return self.puct_search(evaluate, simulations, best=True, **kw)[1]
 
     # ------------------------------------------------------------ exact endgame
     def solve(self, max_empties=10, max_nodes=1 << 22, best=False, move_values=False, status=False, nodes=False):

@@ -446,6 +446,153 @@ int oth_mcts(oth_env *env, const oth_mcts_params *p, void *workspace, uint64_t w
              int32_t *visits, int32_t *wins2, int32_t *best, int32_t *tree_nodes, uint8_t *status,
              oth_stream_t stream);
 
+/* Network-guided tree search per board (no reference counterpart: the rung
+ * after oth_mcts, the search of the AlphaZero loop).  Priors steer the
+ * selection and a value supplied by the caller replaces the playouts; both are
+ * integers, so every output is an exact function of the board, the parameters
+ * and the integers supplied, and the mapping to lanes shows in none of them.
+ * The evaluation (a policy and value network, say) runs between launches: the
+ * tree of a board persists in a workspace the caller supplies, and each
+ * oth_puct_advance carries every board's search one simulation further -- it
+ * applies the evaluation of the board's pending leaf, descends to the next
+ * leaf and emits that leaf as the next input.  E boards give a batch of E
+ * leaves a launch; no random number is drawn.
+ *
+ * Parameters (struct oth_puct_params, host memory, read during the call and
+ * baked into the launch; the same values in every call of one search): the
+ * exploration constant C in 1/256 and T node slots per board.
+ *
+ * The tree.  A node holds a position as oth_step with flags 0 leaves it, a
+ * pass already resolved, exactly as an oth_mcts node.  It also holds
+ *   v  the evaluations backed up through it,
+ *   w  an int64: the sum of the backed-up values, counted for the colour that
+ *      moved into the node (its parent's side to move),
+ *   P  its prior in [0, OTH_PUCT_PRIOR_MAX], its square, and whether its
+ *      position has been made (a child exists from its parent's expansion on;
+ *      its position is computed when a selection first moves to it).
+ * Node 0 is the root and used = 1.
+ *
+ * oth_puct_begin reads the handle's boards, meta and stored possible_moves and
+ * classifies each board as oth_mcts does (oth_solve's status numbers):
+ * TERMINATED, NO_MOVE (live, the stored mask empty), otherwise DONE.  A DONE
+ * board gets its root, the stored mask (its squares on the board) as the
+ * root's move list, and the root is its pending leaf, kind EXPAND (T >= N*N
+ * holds the root's children; a stored mask of more than T - 1 squares, which
+ * no position of the game has, makes it a VALUE leaf).  Other boards have no
+ * pending leaf.  Then the leaves are written (below).
+ *
+ * oth_puct_advance, for each board with a pending leaf L, s being L's side to
+ * move:
+ *  1. Value.  Kind TERMINAL: val = OTH_PUCT_VALUE_ONE sign(discs(s) -
+ *     discs(other)).  Otherwise val = values[e] clamped to [-OTH_PUCT_VALUE_ONE,
+ *     OTH_PUCT_VALUE_ONE]: the value of L for s, in units of 2^-15.
+ *  2. Expand, kind EXPAND only (decided at selection time by used + k <= T, k
+ *     being L's move count): the slots used .. used+k-1 are reserved for L's
+ *     children in ascending square order and used += k.  A child gets its
+ *     square, P = priors[e][square] clamped to [0, OTH_PUCT_PRIOR_MAX], v = w =
+ *     0, and is not made.  Priors at other squares are never read; kinds VALUE
+ *     and TERMINAL read none.
+ *  3. Back up.  Every node on the path but the root: v += 1, and w += val if
+ *     the colour that moved into it is s, else w -= val.  No other sign logic,
+ *     passes included.  The root: v += 1.
+ *  4. Select, if more != 0 and the root's v < OTH_PUCT_MAX_SIMS; otherwise the
+ *     board has no pending leaf afterwards.  From cur = the root, repeat:
+ *       - cur is terminated: stop, kind TERMINAL.
+ *       - cur has no reserved children: stop, kind EXPAND if used + k <= T,
+ *         else VALUE (the tree is full; cur stays a leaf for the rest of the
+ *         search).
+ *       - otherwise move to the child c of the largest key, the lowest square
+ *         among equal keys,
+ *           key = q_c + floor(C P_c isqrt(2^16 v_p) / (2^17 (1 + v_c)))
+ *           q_c = 0 if v_c = 0, else floor(w_c / v_c), rounded toward minus
+ *                 infinity;
+ *         v_p is cur's v (>= 1 whenever cur has children), isqrt the exact
+ *         integer floor square root, keys compared as signed 64-bit integers
+ *         (the numerator is below 2^52).  q is in units of 2^-15 and the second
+ *         term is c P sqrt(v_p) / (1 + v_c) in the same units, c = C / 256 and
+ *         P = P_c / 2^16.  If c is not made, its position is made now
+ *         (oth_step's ply with flags 0, a pass resolved) and c is the leaf:
+ *         stop.
+ * A board without a pending leaf ignores priors, values and more.  The call
+ * never reads the handle's boards: a search goes on from the root it began
+ * with, whatever the handle has done since.
+ *
+ * Leaves (struct oth_puct_leaves, host memory holding device pointers; the
+ * struct or any pointer in it may be NULL; every element of a non-NULL array
+ * is written by begin and by advance).  kind uint8[E], boards uint64[E][2W],
+ * meta uint16[E], legal uint64[E][W] -- the exchange format of oth_get_state /
+ * oth_set_state.  A board with a pending leaf after the call: its kind, and the
+ * leaf's position; meta carries the turn, terminated and winner bits as
+ * oth_step sets them and no opening plies; legal is the leaf's recomputed move
+ * list (none for a terminated leaf, where oth_step on a full board would leave
+ * the mask as it was), for the root the stored mask.  A board without one: kind
+ * OTH_PUCT_LEAF_NONE and the root with the meta the handle held at begin, so
+ * that an evaluator always gets a valid input.  obs (NULL: none), of `layout`
+ * and `dtype`, is exactly what oth_observe(layout, dtype) gives for a handle
+ * oth_set_state'd to these three arrays, (E, planes, N, N).
+ *
+ * oth_puct_result may be called at any point of a search and changes nothing.
+ * visits int32[E][N*N] is required; value_sums int64[E][N*N], best int32[E],
+ * tree_nodes int32[E], status uint8[E] may be NULL; every element of a
+ * non-NULL output is written.  DONE boards: visits[a] / value_sums[a] are the
+ * v / w of the root's child on square a, 0 elsewhere; best is the child with
+ * the most visits, then the larger w, then the lowest square, -1 while no
+ * child has a visit (the root unexpanded, or only the root evaluated);
+ * tree_nodes is used.  TERMINATED and NO_MOVE boards:
+ * zeros, best -1, tree_nodes 1.
+ *
+ * Workspace.  Device memory of at least oth_puct_workspace_bytes(board_size,
+ * n_envs, T) bytes, 8-byte aligned.  It needs no initialising before begin;
+ * between the calls of one search it is opaque and must not be moved or
+ * written (an advance or result on a workspace that no begin of the same
+ * geometry and T wrote does nothing).  One workspace holds one search: it is
+ * not oth_mcts' workspace.  oth_puct_workspace_bytes needs no handle and no
+ * GPU; OTH_EINVAL as oth_mcts_workspace_bytes.
+ *
+ * Handle state.  begin reads boards, meta and the stored possible_moves;
+ * advance and result read only the handle's geometry.  None of the calls reads
+ * or writes the ply counter, the tallies or the graph offsets, and none writes
+ * boards, meta or possible_moves.  Each only enqueues work, never synchronises
+ * the host and is capturable into a HIP graph; no counter is baked in, so one
+ * captured advance replayed S times is S simulations (with the priors and
+ * values its pointers hold at each replay).  An advance places at most one disc
+ * per level of a path that is at most N*N + 1 levels long: its running time is
+ * bounded whatever the input.
+ *
+ * OTH_EINVAL, with nothing launched: NULL params or workspace, NULL visits
+ * (result), NULL priors or values (advance), a field out of range, a
+ * misaligned workspace, an unknown layout or dtype beside a non-NULL obs (all
+ * these before the handle is looked at), a NULL handle, max_tree_nodes below
+ * N*N, workspace_bytes below what oth_puct_workspace_bytes reports.  Every
+ * board size works. */
+#define OTH_PUCT_VALUE_ONE      32768       /* a certain win, in value units */
+#define OTH_PUCT_PRIOR_MAX      65535
+#define OTH_PUCT_MAX_C          65535       /* c_puct in 1/256 */
+#define OTH_PUCT_MAX_TREE_NODES (1 << 24)
+#define OTH_PUCT_MAX_SIMS       ((1 << 24) - 1)
+enum { OTH_PUCT_LEAF_NONE = 0, OTH_PUCT_LEAF_EXPAND = 1, OTH_PUCT_LEAF_VALUE = 2, OTH_PUCT_LEAF_TERMINAL = 3 };
+typedef struct oth_puct_params {
+    int32_t c_puct;          /* C in [0, OTH_PUCT_MAX_C]: exploration constant in 1/256 */
+    int32_t max_tree_nodes;  /* T in [N*N, OTH_PUCT_MAX_TREE_NODES]: node slots per board */
+} oth_puct_params;
+typedef struct oth_puct_leaves {
+    uint8_t  *kind;    /* [E] OTH_PUCT_LEAF_* */
+    uint64_t *boards;  /* [E][2W] */
+    uint16_t *meta;    /* [E] */
+    uint64_t *legal;   /* [E][W] */
+    void     *obs;     /* (E, planes, N, N) of layout and dtype, as oth_observe */
+    int32_t   layout, dtype;
+} oth_puct_leaves;
+int oth_puct_workspace_bytes(int32_t board_size, int32_t n_envs, int32_t max_tree_nodes, uint64_t *bytes);
+int oth_puct_begin(oth_env *env, const oth_puct_params *p, void *workspace, uint64_t workspace_bytes,
+                   const oth_puct_leaves *leaves, oth_stream_t stream);
+int oth_puct_advance(oth_env *env, const oth_puct_params *p, void *workspace, uint64_t workspace_bytes,
+                     const int32_t *priors, const int32_t *values, int32_t more,
+                     const oth_puct_leaves *leaves, oth_stream_t stream);
+int oth_puct_result(oth_env *env, const oth_puct_params *p, void *workspace, uint64_t workspace_bytes,
+                    int32_t *visits, int64_t *value_sums, int32_t *best, int32_t *tree_nodes,
+                    uint8_t *status, oth_stream_t stream);
+
 /* OthelloEnv (othello.py:96-214) for every env: the protagonist's colour per
  * env (protagonist: device int8[E] of +1 white / -1 black, NULL = all white,
  * the reference default) and an embedded opponent played on the device

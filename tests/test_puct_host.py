@@ -1,0 +1,124 @@
+"""The network-guided search's core (csrc/puct.hpp, the text the device kernels
+run, compiled for the host with g++: tests/host/puct_host.cpp) against the
+plain Python integers of tests/puct_ref.py, after every simulation.  Every
+comparison is exact equality."""
+import ctypes
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import puct_ref as pf
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(HERE)
+SRC = os.path.join(HERE, "host", "puct_host.cpp")
+LIB = os.path.join(HERE, "host", "libpuct_host.so")
+HDRS = [os.path.join(ROOT, "gymothelloenv_amd", "csrc", f)
+        for f in ("puct.hpp", "mcts.hpp", "root_tasks.hpp", "bitboard.hpp")]
+
+
+@pytest.fixture(scope="module")
+def hostlib():
+    if not os.path.exists(LIB) or os.path.getmtime(LIB) < max(os.path.getmtime(p) for p in [SRC] + HDRS):
+        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-o", LIB, SRC])
+    L = ctypes.CDLL(LIB)
+    P, I = ctypes.c_void_p, ctypes.c_int
+    L.host_puct_ws_words.argtypes = [I, I, I]
+    L.host_puct_ws_words.restype = ctypes.c_uint64
+    L.host_puct_begin.argtypes = [I, I, I, P, P, P, P, P, P, P, P]
+    L.host_puct_advance.argtypes = [I, I, I, I, P, P, P, I, P, P, P, P]
+    L.host_puct_result.argtypes = [I, I, I, P, P, P, P, P, P]
+    L.host_puct_key.argtypes = [ctypes.c_int64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, I]
+    L.host_puct_key.restype = ctypes.c_int64
+    return L
+
+
+def ptr(a):
+    return a.ctypes.data_as(ctypes.c_void_p)
+
+
+class HostSearch(object):
+    """The three calls of the host build, on a workspace of garbage."""
+
+    def __init__(self, L, s, C, T):
+        self.L, self.n, self.E, self.C, self.T, self.nn = L, s.n, s.E, C, T, s.n * s.n
+        W = s.W
+        self.ws = np.full(L.host_puct_ws_words(s.n, s.E, T), 0xA5A5A5A5A5A5A5A5, dtype=np.uint64)
+        self.kind = np.full(s.E, 7, dtype=np.uint8)
+        self.boards = np.full((s.E, 2 * W), 7, dtype=np.uint64)
+        self.meta = np.full(s.E, 7, dtype=np.uint16)
+        self.legal = np.full((s.E, W), 7, dtype=np.uint64)
+        assert L.host_puct_begin(s.n, s.E, T, ptr(s.boards), ptr(s.meta), ptr(s.legal), ptr(self.ws), ptr(self.kind),
+                                 ptr(self.boards), ptr(self.meta), ptr(self.legal)) == 0
+
+    def leaves(self):
+        return self.kind, self.boards, self.meta, self.legal
+
+    def advance(self, priors, values, more):
+        priors, values = np.ascontiguousarray(priors, dtype=np.int32), np.ascontiguousarray(values, dtype=np.int32)
+        for a in self.leaves():
+            a[...] = 7
+        assert self.L.host_puct_advance(self.n, self.E, self.T, self.C, ptr(self.ws), ptr(priors), ptr(values),
+                                        int(more), ptr(self.kind), ptr(self.boards), ptr(self.meta),
+                                        ptr(self.legal)) == 0
+
+    def result(self):
+        E, nn = self.E, self.nn
+        out = (np.full((E, nn), 7, dtype=np.int32), np.full((E, nn), 7, dtype=np.int64), np.full(E, 7, dtype=np.int32),
+               np.full(E, 7, dtype=np.int32), np.full(E, 7, dtype=np.uint8))
+        assert self.L.host_puct_result(self.n, E, self.T, ptr(self.ws), *[ptr(a) for a in out]) == 0
+        return out
+
+
+def same_leaves(got, want, what):
+    for name, g, w in zip(pf.LEAF_NAMES, got, want):
+        np.testing.assert_array_equal(g, w, err_msg="%s %s" % (what, name))
+
+
+@pytest.mark.parametrize("c", pf.CASES, ids=lambda c: pf.CASE_ID % c)
+def test_exact_against_the_reference(hostlib, c):
+    s, run = pf.case(c)
+    pf.check_case(c, run)
+    n, E, sims, C, T = c
+    hs = HostSearch(hostlib, s, C, T)
+    same_leaves(hs.leaves(), run.leaves[0], "begin")
+    for i in range(sims):
+        if i in (0, sims // 2):  # a result in mid-search changes nothing
+            hs.result()
+        priors, values = pf.hash_eval(hs.boards, hs.meta, n * n)
+        hs.advance(priors, values, i < sims - 1)
+        same_leaves(hs.leaves(), run.leaves[i + 1], "advance %d" % i)
+    for name, g, w in zip(pf.NAMES, hs.result(), run.outputs):
+        np.testing.assert_array_equal(g, w, err_msg=name)
+
+
+def test_key(hostlib):
+    rs = np.random.RandomState(3)
+    rows = [(0, 0, 65535, 1, 65535), (0, 0, 65535, (1 << 24) - 1, 65535), (-32768, 1, 0, 1, 0),
+            (-32768 * 5 + 1, 5, 7, 9, 320), (-1, 3, 100, 3, 320), (1, 3, 100, 3, 320), (-7, 7, 1, 7, 1)]
+    for _ in range(20000):
+        v_c = int(rs.randint(0, 1 << int(rs.randint(1, 24))))
+        w_c = int(rs.randint(-32768 * v_c, 32768 * v_c + 1)) if v_c else 0
+        rows.append((w_c, v_c, int(rs.randint(0, 65536)), int(rs.randint(max(v_c, 1), 1 << 24)),
+                     int(rs.randint(0, 65536))))
+    for w_c, v_c, P_c, v_p, C in rows:
+        assert hostlib.host_puct_key(w_c, v_c, P_c, v_p, C) == pf.key(w_c, v_c, P_c, v_p, C), (w_c, v_c, P_c, v_p, C)
+
+
+def test_the_evaluation_matters(hostlib):
+    """Other priors or another value give another search (the reference's inputs are read)."""
+    c = pf.CASES[1]
+    s, run = pf.case(c)
+    n, E, sims, C, T = c
+
+    def visits(dp, dv):
+        hs = HostSearch(hostlib, s, C, T)
+        for i in range(40):
+            priors, values = pf.hash_eval(hs.boards, hs.meta, n * n)
+            hs.advance(priors + dp, values + dv, i < 39)
+        return hs.result()[0]
+
+    base = visits(0, 0)
+    assert (visits(0, 9000) != base).any() and (visits(np.arange(n * n, dtype=np.int32) * 900, 0) != base).any()
