@@ -18,6 +18,8 @@ terminal/score) as HIP kernels for gfx950 behind a C ABI
     puct_quantize, PuctLeaves,       the network-guided tree search of VecOthelloEnv.puct_begin /
     uniform_evaluator,               puct_advance / puct_result / puct_search: a network's floats as the
     playout_evaluator                search's integers, its leaves, and two evaluators without a network
+    PuctPlay                         one move of self-play on that search's tree (VecOthelloEnv.puct_play:
+                                     puct_pick, step, puct_reroot)
 """
 from ._lib import LIB_PATH, OthelloLibError, load  # noqa: F401
 
@@ -27,7 +29,7 @@ BLACK_DISK, NO_DISK, WHITE_DISK = -1, 0, 1
 def __getattr__(name):
     # lazy: importing the package must not touch the GPU (build() runs on CPU hosts)
     if name in ("VecOthelloEnv", "legal_moves", "default_search_weights", "SearchConfig", "PuctLeaves",
-                "puct_quantize", "uniform_evaluator", "playout_evaluator"):
+                "PuctPlay", "puct_quantize", "uniform_evaluator", "playout_evaluator"):
         from . import vec_env
         return getattr(vec_env, name)
     if name in ("OthelloBaseEnv", "SimpleOthelloEnv", "OthelloEnv"):

@@ -136,6 +136,8 @@ SIGNATURES = {
     "oth_puct_begin": (_I32, [_P, _P, _P, _U64, _P, _P]),
     "oth_puct_advance": (_I32, [_P, _P, _P, _U64, _P, _P, _I32, _P, _P]),
     "oth_puct_result": (_I32, [_P, _P, _P, _U64, _P, _P, _P, _P, _P, _P]),
+    "oth_puct_pick": (_I32, [_P, _P, _P, _U64, _P, _U64, _U32, _U64, _P, _P]),
+    "oth_puct_reroot": (_I32, [_P, _P, _P, _U64, _P, _P, _P, _P, _P]),
     "oth_play_search": (_I32, [_P, _P, _P, _I32, _P, _P, _P, _P, _P]),
     "oth_reset_vs_search": (_I32, [_P, _P, _P, _P, _P]),
     "oth_step_vs_search": (_I32, [_P, _P, _P, _P, _P, _P, _P, _P, _P]),

@@ -6,7 +6,8 @@ compiled once per N (-DOTH_N=4..16) in parallel, csrc/play_rand_n.hip (the
 fused random-play kernels, its own scheduler flags) once per N = 4..11, csrc/playouts_n.hip
 (oth_playouts), csrc/solve_n.hip (oth_solve), csrc/search_n.hip (oth_search),
 csrc/play_search_n.hip (oth_play_search, oth_reset_vs_search, oth_step_vs_search) and
-csrc/mcts_n.hip (oth_mcts) and csrc/puct_n.hip (oth_puct_begin, oth_puct_advance, oth_puct_result) once per N,
+csrc/mcts_n.hip (oth_mcts) and csrc/puct_n.hip (oth_puct_begin, oth_puct_advance, oth_puct_result, oth_puct_pick,
+oth_puct_reroot) once per N,
 csrc/capi.hip holds the C ABI, and the objects are linked into one shared library.
 
 Reproducibility: objects go to a fixed directory (`_objs/`, git-ignored) so the
@@ -90,13 +91,15 @@ def _jobs():
     return max(1, min(n, cap, len(SIZES) + 2))
 
 
-def build(force=False, verbose=True, extra_flags=(), out=OUT, jobs=None, only_sizes=None):
+def build(force=False, verbose=True, extra_flags=(), out=OUT, jobs=None, only_sizes=None, only_units=None):
     """only_sizes (A/B variants of the tools, never the shipped library): compile the
     per-N units of these board sizes only and link the other sizes' objects of the
-    main build (which must exist) -- a variant of one size in a fraction of the time."""
+    main build (which must exist) -- a variant of one size in a fraction of the time.
+    only_units (the same, by source): compile only the units of these sources
+    (("puct_n",): every board size of puct_n.hip) and capi.hip, link the rest."""
     if not force and not needs_build(out, extra_flags):
         return out
-    assert only_sizes is None or out != OUT, "the shipped library is always built whole"
+    assert (only_sizes is None and only_units is None) or out != OUT, "the shipped library is always built whole"
     digest = source_hash(extra_flags, out)
     objdir = OBJDIR if out == OUT else os.path.join(OBJDIR, os.path.splitext(os.path.basename(out))[0])
     shutil.rmtree(objdir, ignore_errors=True)
@@ -132,25 +135,48 @@ def build(force=False, verbose=True, extra_flags=(), out=OUT, jobs=None, only_si
     if verbose:
         print("hipcc %s -> %s (%d units, src %s)" % (" ".join(base[1:]), out, len(units), digest[:16]), flush=True)
     reuse = []
+    if only_units is not None:
+        keep = {os.path.basename(u[1]) for u in units
+                if os.path.basename(u[1]) == "capi.o" or os.path.basename(u[1]).startswith(tuple(only_units))}
     if only_sizes is not None:
         keep = {"capi.o", "masked.o"} | {"kernels_n%d.o" % n for n in only_sizes} | {"play_rand_n%d.o" % n
                                                                                    for n in only_sizes} | {
             "playouts_n%d.o" % n for n in only_sizes} | {"solve_n%d.o" % n for n in only_sizes} | {
             "search_n%d.o" % n for n in only_sizes} | {"play_search_n%d.o" % n for n in only_sizes} | {
             "mcts_n%d.o" % n for n in only_sizes} | {"puct_n%d.o" % n for n in only_sizes}
+    if only_sizes is not None or only_units is not None:
         reuse = [os.path.join(OBJDIR, os.path.basename(u[1])) for u in units if os.path.basename(u[1]) not in keep]
         units = [u for u in units if os.path.basename(u[1]) in keep]
         missing = [o for o in reuse if not os.path.exists(o)]
         if missing:
-            raise RuntimeError("only_sizes needs the main build's objects: %s" % missing[:3])
+            raise RuntimeError("only_sizes / only_units need the main build's objects: %s" % missing[:3])
         if embedded_hash(OUT) != source_hash():  # the reused objects must come from these sources
-            raise RuntimeError("only_sizes reuses the main build's objects: rebuild %s from the current sources "
+            raise RuntimeError("only_sizes / only_units reuse the main build's objects: rebuild %s from the current sources "
                                "first" % OUT)
     with concurrent.futures.ThreadPoolExecutor(jobs or _jobs()) as ex:
         objs = list(ex.map(compile_one, units)) + reuse
     subprocess.check_call([HIPCC, "--offload-arch=%s" % ARCH, "-shared", "-o", out + ".tmp"] + objs, cwd=ROOT)
     os.replace(out + ".tmp", out)
     return out
+
+
+# oth_puct_reroot's one-lane mapping (csrc/puct.hpp OTH_PUCT_REROOT_LANE) as a second library: the
+# GPU tests hold both mappings against the reference, tools/probe_puct_play.py times them
+REROOT_LANE_FLAGS = ("-DOTH_PUCT_REROOT_LANE=1",)
+REROOT_LANE_OUT = os.path.join(HERE, "variants", "liboth_reroot_lane.so")
+
+
+def build_reroot_lane(verbose=True):
+    """The one-lane variant: 14 units of its own on top of the main build's objects where those are
+    there and current, else built whole."""
+    os.makedirs(os.path.dirname(REROOT_LANE_OUT), exist_ok=True)
+    kw = dict(verbose=verbose, extra_flags=REROOT_LANE_FLAGS, out=REROOT_LANE_OUT)
+    try:
+        return build(only_units=("puct_n",), **kw)
+    except RuntimeError as e:
+        if "main build's objects" not in str(e):
+            raise
+        return build(**kw)
 
 
 if __name__ == "__main__":

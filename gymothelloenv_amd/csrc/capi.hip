@@ -529,6 +529,30 @@ int oth_puct_result(oth_env* env, const oth_puct_params* p, void* workspace, uin
     });
 }
 
+int oth_puct_pick(oth_env* env, const oth_puct_params* p, void* workspace, uint64_t workspace_bytes,
+                  const uint8_t* sample, uint64_t seed, uint32_t id_key, uint64_t counter, int32_t* actions,
+                  oth_stream_t stream) {
+    if (!actions) return fail(OTH_EINVAL, "actions is NULL");
+    if (int rc = puct_check(env, p, workspace, workspace_bytes, nullptr)) return rc;
+    if (int rc = use_device(env)) return rc;
+    return with_n(env->n, [&](auto NC) {
+        return launch_puct_pick<decltype(NC)::value>(env, p, workspace, sample, seed, id_key, counter, actions,
+                                                     (hipStream_t)stream);
+    });
+}
+
+int oth_puct_reroot(oth_env* env, const oth_puct_params* p, void* workspace, uint64_t workspace_bytes,
+                    const int32_t* actions, const int32_t* root_priors, uint8_t* kept, const oth_puct_leaves* leaves,
+                    oth_stream_t stream) {
+    if (!actions) return fail(OTH_EINVAL, "actions is NULL");
+    if (int rc = puct_check(env, p, workspace, workspace_bytes, leaves)) return rc;
+    if (int rc = use_device(env)) return rc;
+    return with_n(env->n, [&](auto NC) {
+        return launch_puct_reroot<decltype(NC)::value>(env, p, workspace, actions, root_priors, kept, leaves,
+                                                       (hipStream_t)stream);
+    });
+}
+
 int oth_search(oth_env* env, int32_t depth, const int8_t* weights, int32_t mobility_weight, int32_t terminal_weight,
                uint64_t max_nodes, int32_t* value, int32_t* best, int32_t* move_values, uint8_t* status,
                uint64_t* nodes, oth_stream_t stream) {

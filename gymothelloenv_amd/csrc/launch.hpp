@@ -155,6 +155,12 @@ int launch_puct_advance(oth_env* env, const oth_puct_params* p, void* workspace,
 template <int N>
 int launch_puct_result(oth_env* env, const oth_puct_params* p, void* workspace, int32_t* visits, int64_t* value_sums,
                        int32_t* best, int32_t* tree_nodes, uint8_t* status, hipStream_t st);
+template <int N>
+int launch_puct_pick(oth_env* env, const oth_puct_params* p, void* workspace, const uint8_t* sample, uint64_t seed,
+                     uint32_t id_key, uint64_t counter, int32_t* actions, hipStream_t st);
+template <int N>
+int launch_puct_reroot(oth_env* env, const oth_puct_params* p, void* workspace, const int32_t* actions,
+                       const int32_t* root_priors, uint8_t* kept, const oth_puct_leaves* leaves, hipStream_t st);
 // the 64-bit words of a search's workspace (puct.hpp PuctWs): a tag and a pad, two header words a board, the
 // leaves' boards, moves and meta in exchange format, then T nodes a board of three boards of W words and four more
 constexpr uint64_t puct_workspace_words(int n, uint64_t E, uint64_t T) {

@@ -2,7 +2,10 @@
 // leaves are evaluated outside the library (a policy and value network between
 // launches), one simulation per launch for all boards (the spec is the header's
 // comment on oth_puct_begin: every output is an integer function of the board,
-// the parameters and the integers supplied).
+// the parameters and the integers supplied); and oth_puct_pick / oth_puct_reroot,
+// self-play on that tree: the move of a search, and the search carried to the
+// position the handle has reached, the played child's subtree compacted in
+// place (the header's comment on oth_puct_pick).
 //
 // The workspace, in 64-bit words (PuctWs; E boards, T nodes a board):
 //   [0]                   the tag of the search that began here (puct_tag)
@@ -30,13 +33,17 @@
 // root_tasks.hpp's fill-free solve_flips / solve_legal: the layout, the key, one
 // board's begin / apply / select / leaf / outputs, and the three calls for one
 // board (puct_begin_board, puct_advance_board, puct_result_board), which
-// tests/host/puct_host.cpp compiles with g++ and loops over the boards.
+// tests/host/puct_host.cpp compiles with g++ and loops over the boards; then
+// puct_pick_board and puct_reroot_board (classify, sweep, finish), which
+// tests/host/puct_play_host.cpp compiles the same way.
 //
-// Device mapping: one lane per board runs those three
+// Device mapping: one lane per board runs those
 // functions.  Every word of a board's tree, header and leaf is read and written
 // by that one lane, so there is nothing to fence and no atomic; launches on a
 // stream order one simulation after another.  The observation of the leaves is
 // a second launch of the observation kernels on the workspace's leaf arrays.
+// The one exception is the re-root's compaction, k_puct_reroot_sweep: a wave
+// per board between two lane-per-board launches (its comment has the ordering).
 #pragma once
 #include <math.h>
 
@@ -46,12 +53,23 @@
 // children whose words the selection loads ahead of their keys (1: a load per key)
 #define OTH_PUCT_SELECT_CHUNK 4
 #endif
+#ifndef OTH_PUCT_REROOT_LANE
+// 1: oth_puct_reroot as one launch, a lane per board (k_puct_reroot_lane); 0, the shipped mapping: the
+// compaction on a wave per board between two lane-per-board launches (DESIGN.md sections 4 and 5)
+#define OTH_PUCT_REROOT_LANE 0
+#endif
+#ifndef OTH_PUCT_REROOT_LDS
+// the wave sweep's forwarding table in LDS, in slots (4 bytes each); a longer subtree goes in place on one lane
+#define OTH_PUCT_REROOT_LDS 4096
+#endif
 
 namespace oth {
 
 constexpr int PUCT_VALUE_ONE = 32768, PUCT_PRIOR_MAX = 65535, PUCT_MAX_C = 65535;
 constexpr int PUCT_MAX_TREE_NODES = 1 << 24, PUCT_MAX_SIMS = (1 << 24) - 1;
 constexpr int PUCT_LEAF_NONE = 0, PUCT_LEAF_EXPAND = 1, PUCT_LEAF_VALUE = 2, PUCT_LEAF_TERMINAL = 3;
+constexpr int PUCT_REROOT_KEPT = 0xff;    // a header's kind between the steps of one oth_puct_reroot: the board is kept
+constexpr uint32_t PUCT_RNG_PICK = 4u;    // Philox purpose word of oth_puct_pick's draw (state.hpp RNG_PUCT_PICK)
 
 // floor(num / den) for num < 2^53, 0 < den < 2^53: both are exact in a double, the
 // double's quotient is within one of it, and an integer correction makes it
@@ -115,6 +133,7 @@ struct PuctTree {
     static constexpr int WORDS = 3 * W + 4;
     static constexpr int AT_W = 3 * W, AT_VP = 3 * W + 1, AT_LINK = 3 * W + 2, AT_INFO = 3 * W + 3;
     static constexpr uint32_t F_TURN = 1u, F_MADE = 2u, F_TERM = 4u;
+    static constexpr uint32_t F_KEEP = 8u, F_HEAD = 16u;  // compact()'s marks: set during a re-root's sweep only
 
     uint64_t* t;  // the board's T nodes
     uint32_t used;
@@ -308,6 +327,75 @@ struct PuctTree {
         }
         if (best) *best = ba;
     }
+
+    // oth_puct_pick's move from the root's children: V the sum of their v (0: none, -1); not sampled:
+    // outputs' best; sampled: the first child, in ascending squares, whose cumulative v exceeds
+    // floor(u V / 2^32)
+    OTH_HD int32_t pick_move(bool sample, uint32_t u) const {
+        const uint64_t* root = node(0);
+        const uint32_t first = (uint32_t)root[AT_LINK];
+        const uint32_t k = first && (uint64_t)first + (uint32_t)root[AT_INFO] <= (uint64_t)used ? (uint32_t)root[AT_INFO] : 0u;
+        uint64_t V = 0;
+        for (uint32_t j = 0; j < k; ++j) V += (uint32_t)node(first + j)[AT_VP];
+        if (V == 0) return -1;
+        const uint64_t r = ((uint64_t)u * V) >> 32;
+        uint64_t cum = 0;
+        uint32_t bv = 0;
+        int64_t bw = 0;
+        int32_t ba = -1;
+        for (uint32_t j = 0; j < k; ++j) {
+            const uint64_t* ch = node(first + j);
+            const uint32_t v = (uint32_t)ch[AT_VP];
+            const int64_t w = (int64_t)ch[AT_W];
+            const int32_t a = (int32_t)(flags(first + j) >> 8);
+            if (sample) {
+                cum += v;
+                if (cum > r) return a;
+            } else if (v > 0 && (ba < 0 || v > bv || (v == bv && w > bw))) {
+                ba = a;
+                bv = v;
+                bw = w;
+            }
+        }
+        return ba;
+    }
+
+    // The re-root's compaction in place, one sweep over the slots c .. used - 1: the subtree of c
+    // moves to the slots 0 .. n - 1 in ascending order of the old indices and used = n.  A child's
+    // index is above its parent's and a block of siblings is contiguous, so when the sweep reaches
+    // a member it marks the member's children (F_KEEP; the first of them F_HEAD) and writes its own
+    // new index into their parent halves: a slot above the sweep is never a target (a node's new
+    // index is at most its old one), so the marks wait there untouched.  The first-child half of a
+    // moved node is filled in when the sweep reaches that child (F_HEAD), through the parent's new
+    // index.  The marks are cleared in the moved nodes; slots from n on are free and are written
+    // whole before they are read again (apply).
+    OTH_HD void compact(uint32_t c) {
+        uint32_t n = 0;
+        const uint32_t end = used;
+        for (uint32_t i = c; i < end; ++i) {
+            uint64_t* nd = node(i);
+            const uint64_t info = nd[AT_INFO];
+            const uint32_t f = (uint32_t)(info >> 32);
+            if (i != c && !(f & F_KEEP)) continue;
+            const uint32_t ni = n++;
+            const uint64_t link = nd[AT_LINK];
+            const uint32_t first = (uint32_t)link, k = (uint32_t)info;
+            const uint32_t np = i == c ? 0u : (uint32_t)(link >> 32);  // (already the parent's new index)
+            if (first != 0u && (uint64_t)first + k <= (uint64_t)end) {
+                for (uint32_t j = 0; j < k; ++j) {
+                    uint64_t* ch = node(first + j);
+                    ch[AT_INFO] |= (uint64_t)(F_KEEP | (j == 0 ? F_HEAD : 0u)) << 32;
+                    ch[AT_LINK] = (ch[AT_LINK] & 0xffffffffull) | (uint64_t)ni << 32;
+                }
+            }
+            uint64_t* to = node(ni);
+            for (int j = 0; j < AT_LINK; ++j) to[j] = nd[j];
+            to[AT_LINK] = (uint64_t)np << 32;
+            to[AT_INFO] = info & ~((uint64_t)(F_KEEP | F_HEAD) << 32);
+            if (i != c && (f & F_HEAD)) node(np)[AT_LINK] |= (uint64_t)ni;
+        }
+        used = n;
+    }
 };
 
 // The leaf arrays of board e after a call: the pending leaf, or (kind NONE) the root with the meta
@@ -409,6 +497,110 @@ OTH_HD void puct_result_board(const PuctWs<N>& ws, uint32_t e, int32_t* visits, 
     if (tree_nodes) *tree_nodes = (int32_t)used;
 }
 
+// oth_puct_pick for board e: the move of the search so far (id: the board's global env id + id_key)
+template <int N>
+OTH_HD int32_t puct_pick_board(const PuctWs<N>& ws, uint32_t e, bool sample, uint64_t seed, uint32_t id,
+                               uint64_t counter) {
+    const uint64_t* h = ws.hdr(e);
+    const uint32_t used = (uint32_t)h[0];
+    if ((int)((h[1] >> 8) & 0xffu) != MCTS_DONE || used > ws.T) return -1;
+    const PuctTree<N> tr{ws.tree(e), used};
+    return tr.pick_move(sample, sample ? philox4(seed, id, counter, PUCT_RNG_PICK).x : 0u);
+}
+
+// oth_puct_reroot for board e, in three steps that the device runs as three kernels (a lane, a
+// wave, a lane per board) and puct_reroot_board one after the other.
+//
+// Step 1, the keep test against the handle's black, white, stored possible_moves and meta.  Kept:
+// the header holds used | c << 32 and PUCT_REROOT_KEPT as its kind until step 3; not kept: the
+// board is begun afresh from the handle's position (puct_begin_board, leaves included).
+template <int N>
+OTH_HD bool puct_reroot_classify(const PuctWs<N>& ws, uint32_t e, const uint64_t* black, const uint64_t* white,
+                                 const uint64_t* stored, uint32_t meta, int32_t action, const PuctLeaves& out) {
+    constexpr int W = Geo<N>::W;
+    using Tree = PuctTree<N>;
+    uint64_t* h = ws.hdr(e);
+    const uint64_t h0 = h[0], h1 = h[1];
+    const uint32_t used = (uint32_t)h0;
+    bool keep = false;
+    uint32_t c = 0;
+    if ((int)((h1 >> 8) & 0xffu) == MCTS_DONE && used >= 1u && used <= ws.T && !(meta & 2u)) {
+        const Tree tr{ws.tree(e), used};
+        const uint64_t* root = tr.node(0);
+        const uint32_t first = (uint32_t)root[Tree::AT_LINK], k = (uint32_t)root[Tree::AT_INFO];
+        if (first != 0u && (uint64_t)first + k <= (uint64_t)used)
+            for (uint32_t j = 0; j < k; ++j)
+                if ((int32_t)(tr.flags(first + j) >> 8) == action) c = first + j;
+        if (c != 0u) {
+            if (!(tr.flags(c) & Tree::F_MADE)) tr.make(0u, c);
+            BB<W> B, Wt, mv;
+            tr.position(c, B, Wt, mv);
+            const uint32_t f = tr.flags(c);
+            keep = !(f & Tree::F_TERM) && ((f & Tree::F_TURN) != 0u) == ((meta & 1u) != 0u);
+#pragma unroll
+            for (int i = 0; i < W; ++i)
+                keep = keep && B.w[i] == black[i] && Wt.w[i] == white[i] &&
+                       mv.w[i] == (stored[i] & Geo<N>::BOARD.w[i]);
+        }
+    }
+    if (!keep) {
+        puct_begin_board<N>(ws, e, black, white, stored, meta, out);
+        return false;
+    }
+    h[0] = (uint64_t)used | (uint64_t)c << 32;
+    h[1] = (uint64_t)PUCT_REROOT_KEPT | (uint64_t)(uint32_t)MCTS_DONE << 8 | (uint64_t)(meta & 0xffffu) << 32;
+    return true;
+}
+
+// Step 2 on one lane: the compaction of a kept board (PuctTree::compact)
+template <int N>
+OTH_HD void puct_reroot_sweep(const PuctWs<N>& ws, uint32_t e) {
+    uint64_t* h = ws.hdr(e);
+    const uint64_t h0 = h[0];
+    if ((h[1] & 0xffu) != (uint64_t)PUCT_REROOT_KEPT) return;
+    PuctTree<N> tr{ws.tree(e), (uint32_t)h0};
+    tr.compact((uint32_t)(h0 >> 32));
+    h[0] = (uint64_t)tr.used;
+}
+
+// Step 3: a kept root's new priors (root_priors: the board's N*N, may be null), its selection and the leaves
+template <int N>
+OTH_HD void puct_reroot_finish(const PuctWs<N>& ws, uint32_t e, int C, const int32_t* root_priors, uint8_t* kept,
+                               const PuctLeaves& out) {
+    using Tree = PuctTree<N>;
+    uint64_t* h = ws.hdr(e);
+    const uint64_t h1 = h[1];
+    const bool keep = (h1 & 0xffu) == (uint64_t)PUCT_REROOT_KEPT;
+    if (kept) *kept = keep ? 1 : 0;
+    if (!keep) return;
+    const Tree tr{ws.tree(e), (uint32_t)h[0]};
+    const uint64_t* root = tr.node(0);
+    const uint32_t first = (uint32_t)root[Tree::AT_LINK], k = (uint32_t)root[Tree::AT_INFO];
+    if (root_priors && first != 0u) {
+        for (uint32_t j = 0; j < k; ++j) {
+            uint64_t* ch = tr.node(first + j);
+            const int32_t pr = root_priors[tr.flags(first + j) >> 8];
+            const uint32_t P = (uint32_t)(pr < 0 ? 0 : (pr > PUCT_PRIOR_MAX ? PUCT_PRIOR_MAX : pr));
+            ch[Tree::AT_VP] = (ch[Tree::AT_VP] & 0xffffffffull) | (uint64_t)P << 32;
+        }
+    }
+    int kind = PUCT_LEAF_NONE;
+    uint32_t L = 0u;
+    if ((uint32_t)root[Tree::AT_VP] < (uint32_t)PUCT_MAX_SIMS) L = tr.select(ws.T, C, kind);
+    h[0] = (uint64_t)tr.used | (uint64_t)L << 32;
+    h[1] = (h1 & ~0xffull) | (uint64_t)(uint32_t)kind;
+    puct_write_leaf<N>(ws, e, tr, L, kind, (uint32_t)(h1 >> 32), out);
+}
+
+// oth_puct_reroot for board e: the spec of the call, and the device's one-lane mapping
+template <int N>
+OTH_HD void puct_reroot_board(const PuctWs<N>& ws, uint32_t e, int C, const uint64_t* black, const uint64_t* white,
+                              const uint64_t* stored, uint32_t meta, int32_t action, const int32_t* root_priors,
+                              uint8_t* kept, const PuctLeaves& out) {
+    if (puct_reroot_classify<N>(ws, e, black, white, stored, meta, action, out)) puct_reroot_sweep<N>(ws, e);
+    puct_reroot_finish<N>(ws, e, C, root_priors, kept, out);
+}
+
 }  // namespace oth
 
 #if defined(__HIPCC__)
@@ -423,6 +615,8 @@ static_assert(PUCT_VALUE_ONE == OTH_PUCT_VALUE_ONE && PUCT_PRIOR_MAX == OTH_PUCT
 static_assert(PUCT_LEAF_NONE == OTH_PUCT_LEAF_NONE && PUCT_LEAF_EXPAND == OTH_PUCT_LEAF_EXPAND &&
                   PUCT_LEAF_VALUE == OTH_PUCT_LEAF_VALUE && PUCT_LEAF_TERMINAL == OTH_PUCT_LEAF_TERMINAL,
               "the header's leaf kinds");
+static_assert(PUCT_RNG_PICK == RNG_PUCT_PICK, "state.hpp's purpose word");
+static_assert(OTH_PUCT_REROOT_LDS >= 64 && OTH_PUCT_REROOT_LDS <= 16384, "the forwarding table's share of the LDS");
 
 constexpr int PUCT_BLOCK = 64;  // one wave a block, one lane a board
 
@@ -466,6 +660,145 @@ __global__ __launch_bounds__(PUCT_BLOCK) void k_puct_result(int E, uint32_t T, u
     puct_result_board<N>(ws, (uint32_t)e, visits + (size_t)e * NN, value_sums ? value_sums + (size_t)e * NN : nullptr,
                          best ? best + e : nullptr, tree_nodes ? tree_nodes + e : nullptr,
                          status ? status + e : nullptr);
+}
+
+template <int N>
+__global__ __launch_bounds__(PUCT_BLOCK) void k_puct_pick(int E, uint32_t T, uint64_t* __restrict__ wsp,
+                                                          const uint8_t* __restrict__ sample, uint64_t seed,
+                                                          uint32_t id0, uint64_t counter,
+                                                          int32_t* __restrict__ actions) {
+    const long long e = (long long)blockIdx.x * PUCT_BLOCK + threadIdx.x;
+    const PuctWs<N> ws{wsp, (uint32_t)E, T};
+    if (e >= E || *ws.tag() != puct_tag(N, (uint32_t)E, T)) return;
+    actions[e] = puct_pick_board<N>(ws, (uint32_t)e, sample && sample[e] != 0, seed, id0 + (uint32_t)e, counter);
+}
+
+// oth_puct_reroot, the one-lane mapping: the whole call of a board on its lane (OTH_PUCT_REROOT_LANE)
+template <int N>
+__global__ __launch_bounds__(PUCT_BLOCK) void k_puct_reroot_lane(const uint64_t* __restrict__ boards,
+                                                                 const uint16_t* __restrict__ meta,
+                                                                 const uint64_t* __restrict__ legal, int E, uint32_t T,
+                                                                 int C, uint64_t* __restrict__ wsp,
+                                                                 const int32_t* __restrict__ actions,
+                                                                 const int32_t* __restrict__ root_priors,
+                                                                 uint8_t* __restrict__ kept, PuctLeaves out) {
+    constexpr int W = Geo<N>::W;
+    const long long e = (long long)blockIdx.x * PUCT_BLOCK + threadIdx.x;
+    const PuctWs<N> ws{wsp, (uint32_t)E, T};
+    if (e >= E || *ws.tag() != puct_tag(N, (uint32_t)E, T)) return;
+    puct_reroot_board<N>(ws, (uint32_t)e, C, boards + (size_t)e * 2 * W, boards + (size_t)e * 2 * W + W,
+                         legal + (size_t)e * W, meta[e], actions[e],
+                         root_priors ? root_priors + (size_t)e * (N * N) : nullptr, kept ? kept + e : nullptr, out);
+}
+
+// oth_puct_reroot, the shipped mapping, in three launches: the keep test on a lane per board ...
+template <int N>
+__global__ __launch_bounds__(PUCT_BLOCK) void k_puct_reroot_classify(const uint64_t* __restrict__ boards,
+                                                                     const uint16_t* __restrict__ meta,
+                                                                     const uint64_t* __restrict__ legal, int E,
+                                                                     uint32_t T, uint64_t* __restrict__ wsp,
+                                                                     const int32_t* __restrict__ actions,
+                                                                     PuctLeaves out) {
+    constexpr int W = Geo<N>::W;
+    const long long e = (long long)blockIdx.x * PUCT_BLOCK + threadIdx.x;
+    const PuctWs<N> ws{wsp, (uint32_t)E, T};
+    if (e >= E || *ws.tag() != puct_tag(N, (uint32_t)E, T)) return;
+    puct_reroot_classify<N>(ws, (uint32_t)e, boards + (size_t)e * 2 * W, boards + (size_t)e * 2 * W + W,
+                            legal + (size_t)e * W, meta[e], actions[e], out);
+}
+
+// ... the compaction on a wave per board (block e is board e; a board that is not kept returns at
+// once).  A lane takes one of 64 consecutive slots, from c on.  Pass 1 reads the slots' link words
+// and fills the forwarding table in LDS, fwd[old - c] = the new index or NONE: a slot is a member
+// if its parent is -- from the table when the parent lies in an earlier chunk, by propagating the
+// ballot of the members over the wave until it is stable when it lies in the same chunk (a
+// parent's index is below its child's, so every round decides the lowest open lane at least) --
+// and the new index is the members before the chunk plus the ballot's prefix.  Pass 2 reads the
+// members' nodes into registers, translates both halves of the link word through the table and
+// stores them at their new slots: a new index is at most the old one, so a chunk's targets lie
+// below the next chunk's sources, and within a chunk every source word is in registers (the
+// counter of outstanding loads drained) before the first store.  A subtree of more than
+// OTH_PUCT_REROOT_LDS slots is compacted in place by lane 0 (PuctTree::compact).
+template <int N>
+__global__ __launch_bounds__(64) void k_puct_reroot_sweep(int E, uint32_t T, uint64_t* wsp) {
+    using Tree = PuctTree<N>;
+    constexpr int WORDS = Tree::WORDS;
+    constexpr uint32_t NONE = 0xffffffffu;
+    __shared__ uint32_t fwd[OTH_PUCT_REROOT_LDS];
+    const uint32_t e = blockIdx.x, lane = threadIdx.x;
+    const PuctWs<N> ws{wsp, (uint32_t)E, T};
+    if (*ws.tag() != puct_tag(N, (uint32_t)E, T)) return;
+    uint64_t* h = ws.hdr(e);
+    const uint64_t h0 = h[0];
+    if ((h[1] & 0xffu) != (uint64_t)PUCT_REROOT_KEPT) return;  // (the same for the whole wave)
+    const uint32_t used = (uint32_t)h0, c = (uint32_t)(h0 >> 32);
+    if (c == 0u || c >= used || used > T) return;  // (no classify wrote this)
+    if (used - c > (uint32_t)OTH_PUCT_REROOT_LDS) {
+        if (lane == 0) puct_reroot_sweep<N>(ws, e);
+        return;
+    }
+    uint64_t* t = ws.tree(e);
+    const uint64_t below = (1ull << lane) - 1ull;
+    uint32_t n = 0;  // members before the chunk
+    for (uint32_t b = c; b < used; b += 64u) {
+        const uint32_t i = b + lane;
+        const bool valid = i < used;
+        const uint32_t p = valid ? (uint32_t)(t[(size_t)i * WORDS + Tree::AT_LINK] >> 32) : 0u;
+        bool known = true, mem = false;
+        if (valid) {
+            if (i == c) mem = true;
+            else if (p < c || p >= i) mem = false;  // (p >= i: no tree has it)
+            else if (p < b) mem = fwd[p - c] != NONE;
+            else known = false;  // the parent is a lower lane of this chunk
+        }
+        for (;;) {
+            const uint64_t bk = __ballot(known), bm = __ballot(mem);
+            if (bk == ~0ull) break;
+            if (!known && ((bk >> (p - b)) & 1ull)) {
+                mem = ((bm >> (p - b)) & 1ull) != 0ull;
+                known = true;
+            }
+        }
+        const uint64_t bm = __ballot(mem);
+        if (valid) fwd[i - c] = mem ? n + (uint32_t)__popcll(bm & below) : NONE;
+        n += (uint32_t)__popcll(bm);
+        __syncthreads();
+    }
+    for (uint32_t b = c; b < used; b += 64u) {
+        const uint32_t i = b + lane;
+        const uint32_t ni = i < used ? fwd[i - c] : NONE;
+        uint64_t w[WORDS];
+        if (ni != NONE) {
+            const uint64_t* nd = t + (size_t)i * WORDS;
+#pragma unroll
+            for (int j = 0; j < WORDS; ++j) w[j] = nd[j];
+            const uint32_t first = (uint32_t)w[Tree::AT_LINK], p = (uint32_t)(w[Tree::AT_LINK] >> 32);
+            const uint32_t np = i == c ? 0u : fwd[p - c];
+            const uint32_t nf = first > i && first < used ? fwd[first - c] : 0u;
+            w[Tree::AT_LINK] = (uint64_t)nf | (uint64_t)np << 32;
+        }
+        __builtin_amdgcn_s_waitcnt(0);  // every lane's loads of this chunk have returned
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+        if (ni != NONE) {
+            uint64_t* to = t + (size_t)ni * WORDS;
+#pragma unroll
+            for (int j = 0; j < WORDS; ++j) to[j] = w[j];
+        }
+    }
+    if (lane == 0) h[0] = (uint64_t)n;
+}
+
+// ... and the new priors, the selection and the leaves on a lane per board
+template <int N>
+__global__ __launch_bounds__(PUCT_BLOCK) void k_puct_reroot_finish(int E, uint32_t T, int C,
+                                                                   uint64_t* __restrict__ wsp,
+                                                                   const int32_t* __restrict__ root_priors,
+                                                                   uint8_t* __restrict__ kept, PuctLeaves out) {
+    const long long e = (long long)blockIdx.x * PUCT_BLOCK + threadIdx.x;
+    const PuctWs<N> ws{wsp, (uint32_t)E, T};
+    if (e >= E || *ws.tag() != puct_tag(N, (uint32_t)E, T)) return;
+    puct_reroot_finish<N>(ws, (uint32_t)e, C, root_priors ? root_priors + (size_t)e * (N * N) : nullptr,
+                          kept ? kept + e : nullptr, out);
 }
 
 }  // namespace oth_dev

@@ -1,6 +1,8 @@
 // puct_n.hip -- k_puct_begin, k_puct_advance, k_puct_result (oth_puct_begin /
 // _advance / _result: a tree search per board whose leaves are evaluated between
-// launches, puct.hpp) in a translation unit of its own per board size
+// launches, puct.hpp), k_puct_pick and k_puct_reroot_* (oth_puct_pick /
+// oth_puct_reroot: the self-play move and the tree carried to the played
+// position) in a translation unit of its own per board size
 // (-DOTH_N=4 .. 16), like mcts_n.hip.
 #include "puct.hpp"
 #include "launch.hpp"
@@ -70,10 +72,40 @@ int launch_puct_result(oth_env* env, const oth_puct_params* p, void* workspace, 
     return after_launch("oth_puct_result");
 }
 
+template <int N>
+int launch_puct_pick(oth_env* env, const oth_puct_params* p, void* workspace, const uint8_t* sample, uint64_t seed,
+                     uint32_t id_key, uint64_t counter, int32_t* actions, hipStream_t st) {
+    launch_k(k_puct_pick<N>, dim3(puct_grid(env->E)), dim3(PUCT_BLOCK), 0, st, env->E, (uint32_t)p->max_tree_nodes,
+             reinterpret_cast<uint64_t*>(workspace), sample, seed, id_key + env->id_base, counter, actions);
+    return after_launch("oth_puct_pick");
+}
+
+template <int N>
+int launch_puct_reroot(oth_env* env, const oth_puct_params* p, void* workspace, const int32_t* actions,
+                       const int32_t* root_priors, uint8_t* kept, const oth_puct_leaves* lv, hipStream_t st) {
+    const PuctWs<N> ws{reinterpret_cast<uint64_t*>(workspace), (uint32_t)env->E, (uint32_t)p->max_tree_nodes};
+    const dim3 grid(puct_grid(env->E)), block(PUCT_BLOCK);
+#if OTH_PUCT_REROOT_LANE
+    launch_k(k_puct_reroot_lane<N>, grid, block, 0, st, env->boards, env->meta, env->legal, env->E, ws.T, p->c_puct,
+             ws.base, actions, root_priors, kept, leaves_of(lv));
+#else
+    launch_k(k_puct_reroot_classify<N>, grid, block, 0, st, env->boards, env->meta, env->legal, env->E, ws.T, ws.base,
+             actions, leaves_of(lv));
+    launch_k(k_puct_reroot_sweep<N>, dim3((unsigned)env->E), dim3(64), 0, st, env->E, ws.T, ws.base);
+    launch_k(k_puct_reroot_finish<N>, grid, block, 0, st, env->E, ws.T, p->c_puct, ws.base, root_priors, kept,
+             leaves_of(lv));
+#endif
+    return puct_observe<N>(env, ws, lv, "oth_puct_reroot", st);
+}
+
 template int launch_puct_begin<OTH_N>(oth_env*, const oth_puct_params*, void*, const oth_puct_leaves*, hipStream_t);
 template int launch_puct_advance<OTH_N>(oth_env*, const oth_puct_params*, void*, const int32_t*, const int32_t*, int,
                                         const oth_puct_leaves*, hipStream_t);
 template int launch_puct_result<OTH_N>(oth_env*, const oth_puct_params*, void*, int32_t*, int64_t*, int32_t*, int32_t*,
                                        uint8_t*, hipStream_t);
+template int launch_puct_pick<OTH_N>(oth_env*, const oth_puct_params*, void*, const uint8_t*, uint64_t, uint32_t, uint64_t,
+                                     int32_t*, hipStream_t);
+template int launch_puct_reroot<OTH_N>(oth_env*, const oth_puct_params*, void*, const int32_t*, const int32_t*, uint8_t*,
+                                       const oth_puct_leaves*, hipStream_t);
 
 }  // namespace oth_host

@@ -46,6 +46,8 @@ def _ptr(t):
 
 # the leaves of a network-guided search (VecOthelloEnv.puct_begin / puct_advance)
 PuctLeaves = collections.namedtuple("PuctLeaves", ("kind", "boards", "meta", "legal", "obs"))
+# one move of self-play on the search's tree (VecOthelloEnv.puct_play)
+PuctPlay = collections.namedtuple("PuctPlay", ("actions", "visits", "rewards", "dones", "kept"))
 
 
 def puct_quantize(logits, leaf_legal, values):
@@ -158,6 +160,7 @@ class VecOthelloEnv(object):
         self._okobs = None  # (obs tensor, layout) step() / sample_step() have checked
         self._sample_calls = 0  # Philox counter of sample_actions
         self._playout_calls = 0  # `counter` of the next playouts() call that gives none
+        self._pick_calls = 0  # `counter` of the next sampling puct_pick() call that gives none
         self._mcts_ws = None  # mcts()'s workspace: a uint8 tensor, regrown only when too small
         self._puct_ws = None  # the puct_* search's workspace, its own: mcts() would overwrite a search in progress
         self._puct = None  # the search in progress: (params, the C leaves struct, PuctLeaves)
@@ -789,6 +792,114 @@ class VecOthelloEnv(object):
         for k in ("value_sums", "best", "tree_nodes", "status"):
             kw.pop(k, None)
         return self.puct_search(evaluate, simulations, best=True, **kw)[1]
+
+    # ------------------------------------------------- self-play on the search's tree
+    def puct_pick(self, sample=None, seed=None, counter=None):
+        """The move of the search so far for every board (oth_puct_pick; it changes
+        nothing and may be called at any point): int32 (E,).  sample None or 0 for a
+        board: puct_result's `best`; sample (a bool / uint8 (E,) tensor, or True for
+        every board) nonzero: a square drawn in proportion to the root's children's
+        visits -- temperature 1, the self-play move of the opening plies -- by a
+        stateless Philox draw keyed by (seed, global env id, counter), so a sharded
+        run equals the unsharded one.  -1 for a board that is terminated, has no
+        possible move, or whose root has no visited child yet.  seed=None: the env's
+        seed XOR PLAYOUT_SEED_XOR; counter=None: `puct_pick_counter`, which then
+        moves on by one (only when a sample is asked for)."""
+        p, lv, leaves = self._puct_state()
+        E = self.num_envs
+        sm = None
+        if sample is True:
+            sm = torch.ones(E, dtype=torch.uint8, device=self.device)
+        elif sample is not None and sample is not False:
+            sm = sample.to(device=self.device).ne(0).to(torch.uint8).contiguous()
+            if sm.numel() != E:
+                raise ValueError("sample must have %d elements" % E)
+        key = (self.seed ^ PLAYOUT_SEED_XOR if seed is None else int(seed)) & (2 ** 64 - 1)
+        own = counter is None
+        ctr = self._pick_calls if own else int(counter)
+        if not 0 <= ctr < 2 ** 64:
+            raise ValueError("counter is out of range")
+        actions = self._i32(E)
+        L.check(self._lib.oth_puct_pick(self._h, ctypes.byref(p), _ptr(self._puct_ws), self._puct_ws.numel(), _ptr(sm),
+                                        key, 0, ctr, _ptr(actions), self._stream()), "oth_puct_pick")
+        if own and sm is not None:
+            self._pick_calls += 1
+        return actions
+
+    @property
+    def puct_pick_counter(self):
+        """`counter` of the next sampling puct_pick() call that does not give one."""
+        return self._pick_calls
+
+    @puct_pick_counter.setter
+    def puct_pick_counter(self, v):
+        self._pick_calls = int(v)
+
+    def puct_reroot(self, actions, root_priors=None, kept=False):
+        """Carry the search to the position the handle has reached since it began --
+        normally by step(actions) -- keeping the subtree of the played move
+        (oth_puct_reroot).  actions int32 (E,): the squares that were played.  A
+        board is kept if the root's child on actions[e] is the handle's position
+        (discs, side to move, possible moves) and the game goes on; then that child
+        is the new root, with every node below it as it was, and the rest of the
+        tree's slots are free again.  Any other board -- a game that ended or
+        auto-reset, an action of -1, a handle set elsewhere -- begins afresh from
+        the handle's position, exactly as puct_begin would.  root_priors int32 (E,
+        N*N) (as puct_quantize makes them): the new priors of the kept roots'
+        children, the way to mix root noise in again; fresh roots take theirs at
+        their first advance.  Returns the search's PuctLeaves, rewritten in place
+        with every board's next leaf; with kept=True (the leaves, kept uint8 (E,))."""
+        p, lv, leaves = self._puct_state()
+        E, nn = self.num_envs, self.board_size * self.board_size
+        a = actions.to(device=self.device, dtype=torch.int32).contiguous()
+        if a.numel() != E:
+            raise ValueError("expected %d actions, got %d" % (E, a.numel()))
+        rp = None
+        if root_priors is not None:
+            rp = root_priors.to(device=self.device, dtype=torch.int32).contiguous()
+            if rp.numel() != E * nn:
+                raise ValueError("root_priors must have %d elements" % (E * nn))
+        kp = self._u8(E) if kept else None
+        L.check(self._lib.oth_puct_reroot(self._h, ctypes.byref(p), _ptr(self._puct_ws), self._puct_ws.numel(), _ptr(a),
+                                          _ptr(rp), _ptr(kp), ctypes.byref(lv), self._stream()), "oth_puct_reroot")
+        return (leaves, kp) if kept else leaves
+
+    def puct_play(self, evaluate, simulations, sample=None, **begin_kw):
+        """One move of self-play on every board: puct_begin(**begin_kw) if no search is
+        in progress, `simulations` advances with evaluate(leaves) -> (logits, values)
+        as puct_search runs them (the last with more=False), puct_result's visits,
+        puct_pick(sample), step(actions, observe=False) and puct_reroot(actions), so
+        that the next call goes on from the played child's subtree.  Returns
+        PuctPlay(actions, visits, rewards, dones, kept): visits int32 (E, N*N) is the
+        policy target of the position the move was played from.
+
+        A board whose action is -1 (terminated, without a possible move, or
+        simulations = 1) steps as any action outside possible_moves does: a
+        terminated board is left as it is and reports done (with auto_reset it was
+        reset at its terminal ply and never shows up terminated); a live board takes
+        the invalid-move path -- the mover loses at once under
+        sudden_death_on_invalid_move, otherwise the turn passes.  Its search begins
+        afresh.  max_tree_nodes=None: twice what `simulations` can reserve, since a
+        kept subtree comes on top of a move's own expansions; a full tree only stops
+        growing (VALUE leaves)."""
+        S = int(simulations)
+        if S < 1:
+            raise ValueError("simulations must be >= 1")
+        if self._puct is None:
+            if begin_kw.get("max_tree_nodes") is None:
+                nn = self.board_size * self.board_size
+                begin_kw["max_tree_nodes"] = min(max(nn, 2 * (S * (nn - 4) // 4 + nn)), L.OTH_PUCT_MAX_TREE_NODES)
+            self.puct_begin(**begin_kw)
+        leaves = self._puct[2]
+        for i in range(S):
+            logits, values = evaluate(leaves)
+            priors, vals = puct_quantize(logits, leaves.legal, values)
+            leaves = self.puct_advance(priors, vals, more=i < S - 1)
+        visits = self.puct_result()
+        actions = self.puct_pick(sample)
+        _, rewards, dones, _ = self.step(actions, observe=False)
+        _, kept = self.puct_reroot(actions, kept=True)
+        return PuctPlay(actions, visits, rewards, dones, kept)
 
     # ------------------------------------------------------------ exact endgame
     def solve(self, max_empties=10, max_nodes=1 << 22, best=False, move_values=False, status=False, nodes=False):

@@ -593,6 +593,80 @@ int oth_puct_result(oth_env *env, const oth_puct_params *p, void *workspace, uin
                     int32_t *visits, int64_t *value_sums, int32_t *best, int32_t *tree_nodes,
                     uint8_t *status, oth_stream_t stream);
 
+/* Self-play on the search's tree: the move of a search, and the search carried
+ * to the position the handle has reached since (the outer loop of AlphaZero-
+ * style self-play: advance S times, pick, oth_step, reroot, advance ...).  Both
+ * work on oth_puct_begin's workspace, whose size does not change: the re-root
+ * works in place.
+ *
+ * oth_puct_pick changes nothing, like oth_puct_result, and may be called at any
+ * point of a search.  actions int32[E] is required; sample uint8[E] may be
+ * NULL.  Per board: a status other than DONE gives -1.  Let V be the sum of
+ * the root's children's v; V = 0 (the root unexpanded, or only the root
+ * evaluated) gives -1.  sample NULL or sample[e] = 0: oth_puct_result's best,
+ * exactly.  sample[e] != 0: the move is drawn in proportion to the visits.  u =
+ * word 0 of the Philox4x32-10 block of key `seed` and counter words (id,
+ * counter lo, counter hi, purpose 4) -- a purpose of its own beside the four
+ * of the draws above -- with id = id_key + env_id_base + e mod 2^32; r =
+ * floor(u V / 2^32) (the rule for an index among n choices; V < 2^24, the
+ * product fits 64 bits); the action is the first child, in ascending squares,
+ * whose cumulative v exceeds r.  Any 64-bit counter is accepted, and it is
+ * baked into the launch (a captured pick replays the same draw).  The draw
+ * depends on the global env id and the counter alone: a sharded run equals the
+ * unsharded one.  Temperatures other than 0 and 1 are the caller's business:
+ * compute the move from visits and hand its square to oth_puct_reroot.
+ *
+ * oth_puct_reroot.  The caller has played something on the handle since the
+ * search began, normally oth_step(actions).  The call reads the handle's
+ * boards, meta and stored possible_moves, as begin does; afterwards the root of
+ * every board's search is the handle's position H, with as much of the old tree
+ * as still applies.  actions int32[E] is required; root_priors int32[E][N*N]
+ * and kept uint8[E] may be NULL.  Per board:
+ *  1. Keep test.  All of: the search's status is DONE; the root has reserved
+ *     children and actions[e] is the square of one of them, c; H is not
+ *     terminated; c's position has H's black discs, white discs and side to
+ *     move; c is not terminated; H's stored mask, restricted to the board,
+ *     equals c's recomputed move list.  If c was not yet made its position is
+ *     made first, exactly as a selection does (oth_step's ply with flags 0, a
+ *     pass resolved).  Nothing else is compared: a handle that auto-reset,
+ *     played a random-opening ply, took the invalid-move path or was
+ *     oth_set_state'd elsewhere simply fails the test.
+ *  2. Kept (kept[e] = 1): the subtree of c becomes the tree and c its root.
+ *     Every node of the subtree, made or not, keeps its v, w, P, square, made
+ *     flag, position and its children in ascending square order; used
+ *     (tree_nodes) becomes the number of nodes of the subtree, so the dropped
+ *     slots are free for later expansions.  The root's own w is not observable.
+ *     Node numbers are opaque: nothing observable depends on them.  The meta
+ *     "the handle held at begin" that a NONE leaf shows becomes H's meta.
+ *  3. Not kept (kept[e] = 0): exactly what oth_puct_begin does for this board
+ *     from H -- status TERMINATED or NO_MOVE, or DONE with a fresh root, used =
+ *     1.
+ *  4. Root priors.  Where root_priors is not NULL and a kept root has reserved
+ *     children, each child's P becomes root_priors[e][square] clamped to [0,
+ *     OTH_PUCT_PRIOR_MAX], before the selection of step 5.  Kept roots only: a
+ *     fresh root gets its priors at its first advance.  This is how root noise
+ *     is applied again: evaluate the observation of the stepped handle, mix the
+ *     noise, quantise, pass the result here.
+ *  5. Pending leaf.  Whatever leaf was pending before the call is discarded
+ *     (its node stays as it is and can be selected again).  A DONE board whose
+ *     root's v < OTH_PUCT_MAX_SIMS runs step 4 of oth_puct_advance from the
+ *     root: its pending leaf and kind.  For a fresh or unexpanded root that is
+ *     the root itself, kind EXPAND (or VALUE as at begin) -- a kept root that
+ *     was a VALUE leaf and now has room included.  Other boards have none.
+ *  6. The leaves and obs are written exactly as advance writes them.
+ * OTH_EINVAL, with nothing launched: NULL actions, and everything the other
+ * oth_puct calls refuse.  The call only enqueues work and is capturable; it
+ * writes nothing of the handle; its running time is bounded by used.  Every
+ * output is a function of the board's own tree, its handle state and its
+ * inputs, never of E, the board's index or the mapping to lanes, and two runs
+ * give identical outputs. */
+int oth_puct_pick(oth_env *env, const oth_puct_params *p, void *workspace, uint64_t workspace_bytes,
+                  const uint8_t *sample, uint64_t seed, uint32_t id_key, uint64_t counter,
+                  int32_t *actions, oth_stream_t stream);
+int oth_puct_reroot(oth_env *env, const oth_puct_params *p, void *workspace, uint64_t workspace_bytes,
+                    const int32_t *actions, const int32_t *root_priors, uint8_t *kept,
+                    const oth_puct_leaves *leaves, oth_stream_t stream);
+
 /* OthelloEnv (othello.py:96-214) for every env: the protagonist's colour per
  * env (protagonist: device int8[E] of +1 white / -1 black, NULL = all white,
  * the reference default) and an embedded opponent played on the device
