@@ -49,6 +49,7 @@ OTH_MCTS_DONE, OTH_MCTS_TERMINATED, OTH_MCTS_NO_MOVE = 0, 1, 3
 OTH_PUCT_VALUE_ONE, OTH_PUCT_PRIOR_MAX, OTH_PUCT_MAX_C = 32768, 65535, 65535  # oth_puct_*
 OTH_PUCT_MAX_TREE_NODES, OTH_PUCT_MAX_SIMS = 1 << 24, (1 << 24) - 1
 OTH_PUCT_LEAF_NONE, OTH_PUCT_LEAF_EXPAND, OTH_PUCT_LEAF_VALUE, OTH_PUCT_LEAF_TERMINAL = range(4)
+OTH_PUCT_MAX_LEAVES = 64  # oth_puct_*_batch
 OTH_GRAPH_SLOTS = 64
 OTH_GRAPH_COUNTER_SHIFT = 40
 
@@ -138,6 +139,10 @@ SIGNATURES = {
     "oth_puct_result": (_I32, [_P, _P, _P, _U64, _P, _P, _P, _P, _P, _P]),
     "oth_puct_pick": (_I32, [_P, _P, _P, _U64, _P, _U64, _U32, _U64, _P, _P]),
     "oth_puct_reroot": (_I32, [_P, _P, _P, _U64, _P, _P, _P, _P, _P]),
+    "oth_puct_batch_workspace_bytes": (_I32, [_I32, _I32, _I32, _I32, _P]),
+    "oth_puct_begin_batch": (_I32, [_P, _P, _I32, _P, _U64, _P, _P]),
+    "oth_puct_advance_batch": (_I32, [_P, _P, _I32, _P, _U64, _P, _P, _I32, _P, _P]),
+    "oth_puct_reroot_batch": (_I32, [_P, _P, _I32, _P, _U64, _P, _P, _P, _I32, _P, _P]),
     "oth_play_search": (_I32, [_P, _P, _P, _I32, _P, _P, _P, _P, _P]),
     "oth_reset_vs_search": (_I32, [_P, _P, _P, _P, _P]),
     "oth_step_vs_search": (_I32, [_P, _P, _P, _P, _P, _P, _P, _P, _P]),

@@ -553,6 +553,68 @@ int oth_puct_reroot(oth_env* env, const oth_puct_params* p, void* workspace, uin
     });
 }
 
+int oth_puct_batch_workspace_bytes(int32_t board_size, int32_t n_envs, int32_t max_tree_nodes, int32_t K,
+                                   uint64_t* bytes) {
+    uint64_t plain = 0;
+    if (!bytes) return fail(OTH_EINVAL, "bytes is NULL");
+    if (int rc = oth_puct_workspace_bytes(board_size, n_envs, max_tree_nodes, &plain)) return rc;
+    if (K < 1 || K > OTH_PUCT_MAX_LEAVES) return fail(OTH_EINVAL, "K must be in [1, 64]");
+    *bytes = puct_batch_workspace_words(board_size, (uint64_t)n_envs, (uint64_t)max_tree_nodes, (uint64_t)K) * 8u;
+    return OTH_OK;
+}
+
+namespace {
+
+// What the three batch calls share beyond puct_check, in its order: K and sim_limit need no handle
+int puct_batch_check(const oth_env* env, const oth_puct_params* p, int32_t K, const void* workspace,
+                     uint64_t workspace_bytes, const oth_puct_leaves* leaves, int32_t sim_limit) {
+    if (K < 1 || K > OTH_PUCT_MAX_LEAVES) return fail(OTH_EINVAL, "K must be in [1, 64]");
+    if (sim_limit < 0 || sim_limit > OTH_PUCT_MAX_SIMS) return fail(OTH_EINVAL, "sim_limit must be in [0, 2^24 - 1]");
+    if (int rc = puct_check(env, p, workspace, workspace_bytes, leaves)) return rc;
+    if ((int64_t)env->E * K > 0x7fffffffll) return fail(OTH_EINVAL, "more than 2^31 - 1 rows of leaves: n_envs K");
+    uint64_t need = 0;
+    if (int rc = oth_puct_batch_workspace_bytes(env->n, env->E, p->max_tree_nodes, K, &need)) return rc;
+    if (workspace_bytes < need)
+        return fail(OTH_EINVAL, "workspace_bytes is below what oth_puct_batch_workspace_bytes reports");
+    return OTH_OK;
+}
+
+}  // namespace
+
+int oth_puct_begin_batch(oth_env* env, const oth_puct_params* p, int32_t K, void* workspace, uint64_t workspace_bytes,
+                         const oth_puct_leaves* leaves, oth_stream_t stream) {
+    if (int rc = puct_batch_check(env, p, K, workspace, workspace_bytes, leaves, 0)) return rc;
+    if (int rc = use_device(env)) return rc;
+    return with_n(env->n, [&](auto NC) {
+        return launch_puct_begin_batch<decltype(NC)::value>(env, p, K, workspace, leaves, (hipStream_t)stream);
+    });
+}
+
+int oth_puct_advance_batch(oth_env* env, const oth_puct_params* p, int32_t K, void* workspace,
+                           uint64_t workspace_bytes, const int32_t* priors, const int32_t* values, int32_t sim_limit,
+                           const oth_puct_leaves* leaves, oth_stream_t stream) {
+    if (!priors) return fail(OTH_EINVAL, "priors is NULL");
+    if (!values) return fail(OTH_EINVAL, "values is NULL");
+    if (int rc = puct_batch_check(env, p, K, workspace, workspace_bytes, leaves, sim_limit)) return rc;
+    if (int rc = use_device(env)) return rc;
+    return with_n(env->n, [&](auto NC) {
+        return launch_puct_advance_batch<decltype(NC)::value>(env, p, K, workspace, priors, values, sim_limit, leaves,
+                                                              (hipStream_t)stream);
+    });
+}
+
+int oth_puct_reroot_batch(oth_env* env, const oth_puct_params* p, int32_t K, void* workspace, uint64_t workspace_bytes,
+                          const int32_t* actions, const int32_t* root_priors, uint8_t* kept, int32_t sim_limit,
+                          const oth_puct_leaves* leaves, oth_stream_t stream) {
+    if (!actions) return fail(OTH_EINVAL, "actions is NULL");
+    if (int rc = puct_batch_check(env, p, K, workspace, workspace_bytes, leaves, sim_limit)) return rc;
+    if (int rc = use_device(env)) return rc;
+    return with_n(env->n, [&](auto NC) {
+        return launch_puct_reroot_batch<decltype(NC)::value>(env, p, K, workspace, actions, root_priors, kept,
+                                                             sim_limit, leaves, (hipStream_t)stream);
+    });
+}
+
 int oth_search(oth_env* env, int32_t depth, const int8_t* weights, int32_t mobility_weight, int32_t terminal_weight,
                uint64_t max_nodes, int32_t* value, int32_t* best, int32_t* move_values, uint8_t* status,
                uint64_t* nodes, oth_stream_t stream) {

@@ -161,11 +161,29 @@ int launch_puct_pick(oth_env* env, const oth_puct_params* p, void* workspace, co
 template <int N>
 int launch_puct_reroot(oth_env* env, const oth_puct_params* p, void* workspace, const int32_t* actions,
                        const int32_t* root_priors, uint8_t* kept, const oth_puct_leaves* leaves, hipStream_t st);
+// k_puct_begin_batch / k_puct_advance_batch / k_puct_reroot_*_batch (oth_puct_*_batch: K leaves a board per
+// launch) in puct_n.hip; the observation runs over the extension's E K rows of leaves
+template <int N>
+int launch_puct_begin_batch(oth_env* env, const oth_puct_params* p, int K, void* workspace,
+                            const oth_puct_leaves* leaves, hipStream_t st);
+template <int N>
+int launch_puct_advance_batch(oth_env* env, const oth_puct_params* p, int K, void* workspace, const int32_t* priors,
+                              const int32_t* values, int sim_limit, const oth_puct_leaves* leaves, hipStream_t st);
+template <int N>
+int launch_puct_reroot_batch(oth_env* env, const oth_puct_params* p, int K, void* workspace, const int32_t* actions,
+                             const int32_t* root_priors, uint8_t* kept, int sim_limit, const oth_puct_leaves* leaves,
+                             hipStream_t st);
 // the 64-bit words of a search's workspace (puct.hpp PuctWs): a tag and a pad, two header words a board, the
 // leaves' boards, moves and meta in exchange format, then T nodes a board of three boards of W words and four more
 constexpr uint64_t puct_workspace_words(int n, uint64_t E, uint64_t T) {
     return 2u + 2u * E + 3u * (uint64_t)((n * n + 63) / 64) * E + (E + 3u) / 4u +
            E * T * (uint64_t)(3 * ((n * n + 63) / 64) + 4);
+}
+// ... and of a batch search's (puct.hpp PuctBatchWs): that workspace, then from the next even word two tags, the
+// E K rows of leaves in exchange format and a slot word a row
+constexpr uint64_t puct_batch_workspace_words(int n, uint64_t E, uint64_t T, uint64_t K) {
+    return ((puct_workspace_words(n, E, T) + 1u) & ~1ull) + 2u + 3u * (uint64_t)((n * n + 63) / 64) * E * K +
+           (E * K + 3u) / 4u + E * K;
 }
 
 }  // namespace oth_host

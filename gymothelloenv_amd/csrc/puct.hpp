@@ -29,13 +29,27 @@
 // header comment has the reason).  A node keeps its parent's index: the backup
 // walks the links and the path needs no array.
 //
+// A batch search (oth_puct_begin_batch / _advance_batch / _reroot_batch: K leaves a
+// board per launch under virtual loss, the header's comment on
+// oth_puct_begin_batch) keeps that layout unchanged, a board's header kind NONE
+// throughout, and adds an extension behind it (PuctBatchWs), from the next even word:
+//   [0], [1]              the tags of the batch search: ~puct_tag, puct_batch_tag(K)
+//   then [EK][2W], [EK][W] and ceil(EK / 4): the leaf arrays of the E K rows, as above
+//   then [E][K]           a board's slots: node | kind << 32
+// The paths of a launch's earlier slots are counted in bits 24 .. 31 of a node's v
+// half (v < 2^24, K <= 64) while one board's selection runs, and are taken out
+// again before the call returns: between launches every word is what the plain
+// calls leave, which is why result, pick, compact and the wave sweep read it as it is.
+//
 // The part outside __HIPCC__ is plain host/device code over bitboard.hpp and
 // root_tasks.hpp's fill-free solve_flips / solve_legal: the layout, the key, one
 // board's begin / apply / select / leaf / outputs, and the three calls for one
 // board (puct_begin_board, puct_advance_board, puct_result_board), which
 // tests/host/puct_host.cpp compiles with g++ and loops over the boards; then
 // puct_pick_board and puct_reroot_board (classify, sweep, finish), which
-// tests/host/puct_play_host.cpp compiles the same way.
+// tests/host/puct_play_host.cpp compiles the same way; and the batch calls for one
+// board (puct_begin_batch_board, puct_advance_batch_board, puct_reroot_finish_batch),
+// which tests/host/puct_batch_host.cpp compiles.
 //
 // Device mapping: one lane per board runs those
 // functions.  Every word of a board's tree, header and leaf is read and written
@@ -68,6 +82,7 @@ namespace oth {
 constexpr int PUCT_VALUE_ONE = 32768, PUCT_PRIOR_MAX = 65535, PUCT_MAX_C = 65535;
 constexpr int PUCT_MAX_TREE_NODES = 1 << 24, PUCT_MAX_SIMS = (1 << 24) - 1;
 constexpr int PUCT_LEAF_NONE = 0, PUCT_LEAF_EXPAND = 1, PUCT_LEAF_VALUE = 2, PUCT_LEAF_TERMINAL = 3;
+constexpr int PUCT_MAX_LEAVES = 64;       // slots a board in a batch call
 constexpr int PUCT_REROOT_KEPT = 0xff;    // a header's kind between the steps of one oth_puct_reroot: the board is kept
 constexpr uint32_t PUCT_RNG_PICK = 4u;    // Philox purpose word of oth_puct_pick's draw (state.hpp RNG_PUCT_PICK)
 
@@ -104,6 +119,13 @@ OTH_HD uint64_t puct_tag(int n, uint32_t E, uint32_t T) {
     return 0x7075637400000000ull ^ ((uint64_t)(uint32_t)n << 56) ^ ((uint64_t)T << 32) ^ (uint64_t)E;
 }
 
+// a batch search's workspace: the plain one, then from the next even word the extension
+constexpr uint64_t puct_batch_ext_word(int n, uint64_t E, uint64_t T) { return (puct_ws_words(n, E, T) + 1u) & ~1ull; }
+constexpr uint64_t puct_batch_ws_words(int n, uint64_t E, uint64_t T, uint64_t K) {
+    return puct_batch_ext_word(n, E, T) + 2u + 3u * (uint64_t)((n * n + 63) / 64) * E * K + (E * K + 3u) / 4u + E * K;
+}
+OTH_HD uint64_t puct_batch_tag(uint32_t K) { return 0x7075637462617400ull | (uint64_t)K; }
+
 template <int N>
 struct PuctWs {
     static constexpr int W = Geo<N>::W;
@@ -116,6 +138,31 @@ struct PuctWs {
     OTH_HD uint16_t* leaf_meta() const { return reinterpret_cast<uint16_t*>(leaf_legal() + W * (size_t)E); }
     OTH_HD uint64_t* tree(uint32_t e) const {
         return leaf_legal() + W * (size_t)E + ((size_t)E + 3) / 4 + (size_t)e * T * (size_t)puct_node_words(N);
+    }
+};
+
+// the extension of a batch search behind PuctWs: R = E K rows of leaves (the accessors' names are
+// PuctWs' own, so that puct_write_leaf serves both)
+template <int N>
+struct PuctBatchWs {
+    static constexpr int W = Geo<N>::W;
+    PuctWs<N> plain;
+    uint32_t K;
+    OTH_HD size_t rows() const { return (size_t)plain.E * K; }
+    OTH_HD uint64_t* ext() const { return plain.base + puct_batch_ext_word(N, plain.E, plain.T); }
+    OTH_HD uint64_t* leaf_boards() const { return ext() + 2; }
+    OTH_HD uint64_t* leaf_legal() const { return leaf_boards() + 2 * W * rows(); }
+    OTH_HD uint16_t* leaf_meta() const { return reinterpret_cast<uint16_t*>(leaf_legal() + W * rows()); }
+    OTH_HD uint64_t* slots(uint32_t e) const { return leaf_legal() + W * rows() + (rows() + 3) / 4 + (size_t)e * K; }
+    OTH_HD void put_tags() const {
+        *plain.tag() = puct_tag(N, plain.E, plain.T);
+        ext()[0] = ~puct_tag(N, plain.E, plain.T);
+        ext()[1] = puct_batch_tag(K);
+    }
+    // a begin_batch of this geometry, T and K wrote the workspace
+    OTH_HD bool begun() const {
+        return *plain.tag() == puct_tag(N, plain.E, plain.T) && ext()[0] == ~puct_tag(N, plain.E, plain.T) &&
+               ext()[1] == puct_batch_tag(K);
     }
 };
 
@@ -290,6 +337,75 @@ struct PuctTree {
         return cur;
     }
 
+    // The selection of one slot of a batch call: select() with every statistic read through the
+    // launch's virtual loss, n the paths of earlier slots through a node (bits 24 .. 31 of its v
+    // half): v' = v + n, w' = w - PUCT_VALUE_ONE n.  r: the slots reserved so far, this launch's
+    // earlier EXPAND leaves included.  kind NONE: the node is already an earlier slot's leaf (no
+    // children, not terminated, n > 0), a collision.  With no count set anywhere this is select().
+    static constexpr uint32_t V_MASK = 0xffffffu;
+    static constexpr int N_SHIFT = 24;
+    OTH_HD uint32_t select_vl(uint32_t T, int C, uint32_t& r, int& kind) const {
+        uint32_t cur = 0;
+        for (int level = 0; level < NN + 2; ++level) {
+            const uint64_t* nd = node(cur);
+            const uint32_t first = (uint32_t)nd[AT_LINK];
+            if ((flags(cur) & F_TERM) || first == 0u) break;
+            const uint32_t k = (uint32_t)nd[AT_INFO];
+            const uint32_t pv = (uint32_t)nd[AT_VP];
+            const uint64_t cs = (uint64_t)(uint32_t)C * mcts_isqrt((uint64_t)((pv & V_MASK) + (pv >> N_SHIFT)) << 16);
+            int64_t bk = 0;
+            uint32_t bi = first;
+            for (uint32_t j0 = 0; j0 < k; j0 += OTH_PUCT_SELECT_CHUNK) {  // (select()'s loads ahead of the keys)
+                uint64_t vp[OTH_PUCT_SELECT_CHUNK], cw[OTH_PUCT_SELECT_CHUNK];
+#pragma unroll
+                for (uint32_t u = 0; u < OTH_PUCT_SELECT_CHUNK; ++u) {
+                    const uint64_t* ch = node(first + (j0 + u < k ? j0 + u : k - 1u));
+                    vp[u] = ch[AT_VP];
+                    cw[u] = ch[AT_W];
+                }
+#pragma unroll
+                for (uint32_t u = 0; u < OTH_PUCT_SELECT_CHUNK; ++u) {
+                    const uint32_t j = j0 + u;
+                    const uint32_t lo = (uint32_t)vp[u], n = lo >> N_SHIFT;
+                    const int64_t key = puct_key((int64_t)cw[u] - (int64_t)PUCT_VALUE_ONE * (int64_t)n, (lo & V_MASK) + n,
+                                                 (uint32_t)(vp[u] >> 32), cs);
+                    if (j < k && (j == 0 || key > bk)) {
+                        bk = key;
+                        bi = first + j;
+                    }
+                }
+            }
+            if (!(flags(bi) & F_MADE)) {
+                make(cur, bi);
+                cur = bi;
+                break;
+            }
+            cur = bi;
+        }
+        const uint64_t info = node(cur)[AT_INFO];
+        if ((uint32_t)(info >> 32) & F_TERM) {
+            kind = PUCT_LEAF_TERMINAL;
+        } else if ((uint32_t)node(cur)[AT_VP] >> N_SHIFT) {
+            kind = PUCT_LEAF_NONE;
+        } else if ((uint64_t)r + (uint32_t)info <= (uint64_t)T) {
+            kind = PUCT_LEAF_EXPAND;
+            r += (uint32_t)info;
+        } else {
+            kind = PUCT_LEAF_VALUE;
+        }
+        return cur;
+    }
+
+    // one path more (d = 1) or less (d = -1) through every node from L up to the root
+    OTH_HD void count_path(uint32_t L, int d) const {
+        const uint64_t one = 1ull << N_SHIFT;
+        for (uint32_t cur = L;; cur = (uint32_t)(node(cur)[AT_LINK] >> 32)) {
+            uint64_t* c = node(cur);
+            c[AT_VP] = d > 0 ? c[AT_VP] + one : c[AT_VP] - one;
+            if (cur == 0u) break;
+        }
+    }
+
     // node i as a leaf in exchange format: turn, terminated and winner bits as oth_step sets them
     OTH_HD void leaf(uint32_t i, BB<W>& black, BB<W>& white, BB<W>& moves, uint32_t& meta) const {
         position(i, black, white, moves);
@@ -400,8 +516,9 @@ struct PuctTree {
 
 // The leaf arrays of board e after a call: the pending leaf, or (kind NONE) the root with the meta
 // the handle held at begin; into the workspace's arrays and the caller's.
-template <int N>
-OTH_HD void puct_write_leaf(const PuctWs<N>& ws, uint32_t e, const PuctTree<N>& tr, uint32_t L, int kind,
+// (Ws: PuctWs<N>, row e = the board; or PuctBatchWs<N>, row e = board K + slot)
+template <int N, class Ws>
+OTH_HD void puct_write_leaf(const Ws& ws, size_t e, const PuctTree<N>& tr, uint32_t L, int kind,
                             uint32_t root_meta, const PuctLeaves& out) {
     constexpr int W = Geo<N>::W;
     BB<W> B, Wt, Lg;
@@ -412,18 +529,18 @@ OTH_HD void puct_write_leaf(const PuctWs<N>& ws, uint32_t e, const PuctTree<N>& 
     } else {
         tr.leaf(L, B, Wt, Lg, meta);
     }
-    uint64_t* lb = ws.leaf_boards() + (size_t)e * 2 * W;
-    uint64_t* ll = ws.leaf_legal() + (size_t)e * W;
+    uint64_t* lb = ws.leaf_boards() + e * 2 * W;
+    uint64_t* ll = ws.leaf_legal() + e * W;
 #pragma unroll
     for (int j = 0; j < W; ++j) {
         lb[j] = B.w[j];
         lb[W + j] = Wt.w[j];
         ll[j] = Lg.w[j];
         if (out.boards) {
-            out.boards[(size_t)e * 2 * W + j] = B.w[j];
-            out.boards[(size_t)e * 2 * W + W + j] = Wt.w[j];
+            out.boards[e * 2 * W + j] = B.w[j];
+            out.boards[e * 2 * W + W + j] = Wt.w[j];
         }
-        if (out.legal) out.legal[(size_t)e * W + j] = Lg.w[j];
+        if (out.legal) out.legal[e * W + j] = Lg.w[j];
     }
     ws.leaf_meta()[e] = (uint16_t)meta;
     if (out.meta) out.meta[e] = (uint16_t)meta;
@@ -563,6 +680,22 @@ OTH_HD void puct_reroot_sweep(const PuctWs<N>& ws, uint32_t e) {
     h[0] = (uint64_t)tr.used;
 }
 
+// step 4 of the re-root: the new priors of a kept root's children (root_priors: the board's N*N, may be null)
+template <int N>
+OTH_HD void puct_root_priors(const PuctTree<N>& tr, const int32_t* root_priors) {
+    using Tree = PuctTree<N>;
+    const uint64_t* root = tr.node(0);
+    const uint32_t first = (uint32_t)root[Tree::AT_LINK], k = (uint32_t)root[Tree::AT_INFO];
+    if (root_priors && first != 0u) {
+        for (uint32_t j = 0; j < k; ++j) {
+            uint64_t* ch = tr.node(first + j);
+            const int32_t pr = root_priors[tr.flags(first + j) >> 8];
+            const uint32_t P = (uint32_t)(pr < 0 ? 0 : (pr > PUCT_PRIOR_MAX ? PUCT_PRIOR_MAX : pr));
+            ch[Tree::AT_VP] = (ch[Tree::AT_VP] & 0xffffffffull) | (uint64_t)P << 32;
+        }
+    }
+}
+
 // Step 3: a kept root's new priors (root_priors: the board's N*N, may be null), its selection and the leaves
 template <int N>
 OTH_HD void puct_reroot_finish(const PuctWs<N>& ws, uint32_t e, int C, const int32_t* root_priors, uint8_t* kept,
@@ -575,15 +708,7 @@ OTH_HD void puct_reroot_finish(const PuctWs<N>& ws, uint32_t e, int C, const int
     if (!keep) return;
     const Tree tr{ws.tree(e), (uint32_t)h[0]};
     const uint64_t* root = tr.node(0);
-    const uint32_t first = (uint32_t)root[Tree::AT_LINK], k = (uint32_t)root[Tree::AT_INFO];
-    if (root_priors && first != 0u) {
-        for (uint32_t j = 0; j < k; ++j) {
-            uint64_t* ch = tr.node(first + j);
-            const int32_t pr = root_priors[tr.flags(first + j) >> 8];
-            const uint32_t P = (uint32_t)(pr < 0 ? 0 : (pr > PUCT_PRIOR_MAX ? PUCT_PRIOR_MAX : pr));
-            ch[Tree::AT_VP] = (ch[Tree::AT_VP] & 0xffffffffull) | (uint64_t)P << 32;
-        }
-    }
+    puct_root_priors<N>(tr, root_priors);
     int kind = PUCT_LEAF_NONE;
     uint32_t L = 0u;
     if ((uint32_t)root[Tree::AT_VP] < (uint32_t)PUCT_MAX_SIMS) L = tr.select(ws.T, C, kind);
@@ -601,6 +726,114 @@ OTH_HD void puct_reroot_board(const PuctWs<N>& ws, uint32_t e, int C, const uint
     puct_reroot_finish<N>(ws, e, C, root_priors, kept, out);
 }
 
+// ---- the batch calls: K slots a board, row e K + j of the leaf arrays is slot j of board e ----
+
+// The leaves of board e's K slots after a batch call, into the extension's arrays and the caller's
+template <int N>
+OTH_HD void puct_write_slots(const PuctBatchWs<N>& bw, uint32_t e, const PuctTree<N>& tr, uint32_t root_meta,
+                             const PuctLeaves& out) {
+    const uint64_t* sl = bw.slots(e);
+    for (uint32_t j = 0; j < bw.K; ++j)
+        puct_write_leaf<N>(bw, (size_t)e * bw.K + j, tr, (uint32_t)sl[j], (int)(sl[j] >> 32), root_meta, out);
+}
+
+// The Select of a batch call for board e (a DONE board's tree): slot after slot in ascending order under
+// the launch's virtual loss, which is taken out again before the function returns
+template <int N>
+OTH_HD void puct_select_slots(const PuctBatchWs<N>& bw, uint32_t e, const PuctTree<N>& tr, int C, uint32_t sim_limit) {
+    uint64_t* sl = bw.slots(e);
+    const uint32_t v0 = (uint32_t)tr.node(0)[PuctTree<N>::AT_VP];
+    uint32_t r = tr.used;
+    bool open = true;
+    for (uint32_t j = 0; j < bw.K; ++j) {
+        uint32_t L = 0u;
+        int kind = PUCT_LEAF_NONE;
+        if (open && (uint64_t)v0 + j < (uint64_t)sim_limit) {
+            L = tr.select_vl(bw.plain.T, C, r, kind);
+            if (kind == PUCT_LEAF_NONE) L = 0u, open = false;  // a collision closes the board for this launch
+            else if (j + 1u < bw.K) tr.count_path(L, 1);      // (no slot reads the last one's path)
+        }
+        sl[j] = (uint64_t)L | (uint64_t)(uint32_t)kind << 32;
+    }
+    for (uint32_t j = 0; j + 1u < bw.K; ++j)
+        if ((uint32_t)(sl[j] >> 32) != (uint32_t)PUCT_LEAF_NONE) tr.count_path((uint32_t)sl[j], -1);
+}
+
+// oth_puct_begin_batch for board e: puct_begin_board, the root as slot 0's leaf
+template <int N>
+OTH_HD void puct_begin_batch_board(const PuctBatchWs<N>& bw, uint32_t e, const uint64_t* black, const uint64_t* white,
+                                   const uint64_t* stored, uint32_t meta, const PuctLeaves& out) {
+    const PuctWs<N>& ws = bw.plain;
+    puct_begin_board<N>(ws, e, black, white, stored, meta, PuctLeaves{nullptr, nullptr, nullptr, nullptr});
+    uint64_t* h = ws.hdr(e);
+    const uint64_t h1 = h[1];
+    uint64_t* sl = bw.slots(e);
+    sl[0] = (h1 & 0xffull) << 32;
+    for (uint32_t j = 1; j < bw.K; ++j) sl[j] = 0ull;
+    h[1] = h1 & ~0xffull;  // (kind NONE in the header: a plain advance does nothing to this board)
+    puct_write_slots<N>(bw, e, PuctTree<N>{ws.tree(e), 1u}, (uint32_t)(h1 >> 32), out);
+}
+
+// oth_puct_advance_batch for board e.  priors: the board's K rows of N*N; values: its K
+template <int N>
+OTH_HD void puct_advance_batch_board(const PuctBatchWs<N>& bw, uint32_t e, int C, const int32_t* priors,
+                                     const int32_t* values, uint32_t sim_limit, const PuctLeaves& out) {
+    const PuctWs<N>& ws = bw.plain;
+    uint64_t* h = ws.hdr(e);
+    const uint64_t h1 = h[1];
+    PuctTree<N> tr{ws.tree(e), (uint32_t)h[0]};
+    uint64_t* sl = bw.slots(e);
+    bool any = false;
+    for (uint32_t j = 0; j < bw.K; ++j) {  // Apply, in slot order
+        const uint32_t L = (uint32_t)sl[j];
+        const int kind = (int)(sl[j] >> 32);
+        if (kind < PUCT_LEAF_EXPAND || kind > PUCT_LEAF_TERMINAL || L >= tr.used || tr.used > ws.T) {
+            sl[j] = 0ull;  // (no leaf; or a slot no batch call wrote: nothing is followed)
+            continue;
+        }
+        tr.apply(L, kind, ws.T, priors + (size_t)j * (N * N), values[j]);
+        any = true;
+    }
+    if (any) {
+        puct_select_slots<N>(bw, e, tr, C, sim_limit);
+        h[0] = (uint64_t)tr.used;
+    }
+    puct_write_slots<N>(bw, e, tr, (uint32_t)(h1 >> 32), out);
+}
+
+// oth_puct_reroot_batch's step after puct_reroot_classify and the sweep: the slots' leaves are
+// discarded, a kept root takes its new priors, and a DONE board, kept or fresh, runs the Select
+template <int N>
+OTH_HD void puct_reroot_finish_batch(const PuctBatchWs<N>& bw, uint32_t e, int C, const int32_t* root_priors,
+                                     uint8_t* kept, uint32_t sim_limit, const PuctLeaves& out) {
+    const PuctWs<N>& ws = bw.plain;
+    uint64_t* h = ws.hdr(e);
+    const uint64_t h1 = h[1];
+    const bool keep = (h1 & 0xffu) == (uint64_t)PUCT_REROOT_KEPT;
+    if (kept) *kept = keep ? 1 : 0;
+    const PuctTree<N> tr{ws.tree(e), (uint32_t)h[0]};
+    uint64_t* sl = bw.slots(e);
+    for (uint32_t j = 0; j < bw.K; ++j) sl[j] = 0ull;
+    if (keep) puct_root_priors<N>(tr, root_priors);
+    if ((int)((h1 >> 8) & 0xffu) == MCTS_DONE && tr.used >= 1u && tr.used <= ws.T)
+        puct_select_slots<N>(bw, e, tr, C, sim_limit);
+    h[0] = (uint64_t)tr.used;
+    h[1] = h1 & ~0xffull;
+    puct_write_slots<N>(bw, e, tr, (uint32_t)(h1 >> 32), out);
+}
+
+// oth_puct_reroot_batch for board e: the spec of the call
+template <int N>
+OTH_HD void puct_reroot_batch_board(const PuctBatchWs<N>& bw, uint32_t e, int C, const uint64_t* black,
+                                    const uint64_t* white, const uint64_t* stored, uint32_t meta, int32_t action,
+                                    const int32_t* root_priors, uint8_t* kept, uint32_t sim_limit,
+                                    const PuctLeaves& out) {
+    if (puct_reroot_classify<N>(bw.plain, e, black, white, stored, meta, action,
+                                PuctLeaves{nullptr, nullptr, nullptr, nullptr}))
+        puct_reroot_sweep<N>(bw.plain, e);
+    puct_reroot_finish_batch<N>(bw, e, C, root_priors, kept, sim_limit, out);
+}
+
 }  // namespace oth
 
 #if defined(__HIPCC__)
@@ -610,7 +843,7 @@ namespace oth_dev {
 
 static_assert(PUCT_VALUE_ONE == OTH_PUCT_VALUE_ONE && PUCT_PRIOR_MAX == OTH_PUCT_PRIOR_MAX &&
                   PUCT_MAX_C == OTH_PUCT_MAX_C && PUCT_MAX_TREE_NODES == OTH_PUCT_MAX_TREE_NODES &&
-                  PUCT_MAX_SIMS == OTH_PUCT_MAX_SIMS,
+                  PUCT_MAX_SIMS == OTH_PUCT_MAX_SIMS && PUCT_MAX_LEAVES == OTH_PUCT_MAX_LEAVES,
               "the header's limits");
 static_assert(PUCT_LEAF_NONE == OTH_PUCT_LEAF_NONE && PUCT_LEAF_EXPAND == OTH_PUCT_LEAF_EXPAND &&
                   PUCT_LEAF_VALUE == OTH_PUCT_LEAF_VALUE && PUCT_LEAF_TERMINAL == OTH_PUCT_LEAF_TERMINAL,
@@ -720,14 +953,12 @@ __global__ __launch_bounds__(PUCT_BLOCK) void k_puct_reroot_classify(const uint6
 // counter of outstanding loads drained) before the first store.  A subtree of more than
 // OTH_PUCT_REROOT_LDS slots is compacted in place by lane 0 (PuctTree::compact).
 template <int N>
-__global__ __launch_bounds__(64) void k_puct_reroot_sweep(int E, uint32_t T, uint64_t* wsp) {
+__device__ __forceinline__ void puct_sweep_wave(const PuctWs<N>& ws, uint32_t* fwd) {
     using Tree = PuctTree<N>;
     constexpr int WORDS = Tree::WORDS;
     constexpr uint32_t NONE = 0xffffffffu;
-    __shared__ uint32_t fwd[OTH_PUCT_REROOT_LDS];
     const uint32_t e = blockIdx.x, lane = threadIdx.x;
-    const PuctWs<N> ws{wsp, (uint32_t)E, T};
-    if (*ws.tag() != puct_tag(N, (uint32_t)E, T)) return;
+    const uint32_t T = ws.T;
     uint64_t* h = ws.hdr(e);
     const uint64_t h0 = h[0];
     if ((h[1] & 0xffu) != (uint64_t)PUCT_REROOT_KEPT) return;  // (the same for the whole wave)
@@ -788,6 +1019,14 @@ __global__ __launch_bounds__(64) void k_puct_reroot_sweep(int E, uint32_t T, uin
     if (lane == 0) h[0] = (uint64_t)n;
 }
 
+template <int N>
+__global__ __launch_bounds__(64) void k_puct_reroot_sweep(int E, uint32_t T, uint64_t* wsp) {
+    __shared__ uint32_t fwd[OTH_PUCT_REROOT_LDS];
+    const PuctWs<N> ws{wsp, (uint32_t)E, T};
+    if (*ws.tag() != puct_tag(N, (uint32_t)E, T)) return;
+    puct_sweep_wave<N>(ws, fwd);
+}
+
 // ... and the new priors, the selection and the leaves on a lane per board
 template <int N>
 __global__ __launch_bounds__(PUCT_BLOCK) void k_puct_reroot_finish(int E, uint32_t T, int C,
@@ -799,6 +1038,79 @@ __global__ __launch_bounds__(PUCT_BLOCK) void k_puct_reroot_finish(int E, uint32
     if (e >= E || *ws.tag() != puct_tag(N, (uint32_t)E, T)) return;
     puct_reroot_finish<N>(ws, (uint32_t)e, C, root_priors ? root_priors + (size_t)e * (N * N) : nullptr,
                           kept ? kept + e : nullptr, out);
+}
+
+// ---- the batch calls (oth_puct_begin_batch / _advance_batch / _reroot_batch): a lane per board runs the
+// board's K slots one after the other -- the selection is sequential by definition -- so, as in the plain
+// calls, one lane owns every word of its board, its slots and its K rows of leaves.  (A workspace that no
+// begin_batch of this geometry, T and K wrote is left alone.)
+
+template <int N>
+__global__ __launch_bounds__(PUCT_BLOCK) void k_puct_begin_batch(const uint64_t* __restrict__ boards,
+                                                                 const uint16_t* __restrict__ meta,
+                                                                 const uint64_t* __restrict__ legal, int E, uint32_t T,
+                                                                 uint32_t K, uint64_t* __restrict__ wsp,
+                                                                 PuctLeaves out) {
+    constexpr int W = Geo<N>::W;
+    const long long e = (long long)blockIdx.x * PUCT_BLOCK + threadIdx.x;
+    const PuctBatchWs<N> bw{PuctWs<N>{wsp, (uint32_t)E, T}, K};
+    if (e == 0) bw.put_tags();
+    if (e >= E) return;
+    puct_begin_batch_board<N>(bw, (uint32_t)e, boards + (size_t)e * 2 * W, boards + (size_t)e * 2 * W + W,
+                              legal + (size_t)e * W, meta[e], out);
+}
+
+template <int N>
+__global__ __launch_bounds__(PUCT_BLOCK) void k_puct_advance_batch(int E, uint32_t T, uint32_t K, int C,
+                                                                   uint64_t* __restrict__ wsp,
+                                                                   const int32_t* __restrict__ priors,
+                                                                   const int32_t* __restrict__ values,
+                                                                   uint32_t sim_limit, PuctLeaves out) {
+    const long long e = (long long)blockIdx.x * PUCT_BLOCK + threadIdx.x;
+    const PuctBatchWs<N> bw{PuctWs<N>{wsp, (uint32_t)E, T}, K};
+    if (e >= E || !bw.begun()) return;
+    puct_advance_batch_board<N>(bw, (uint32_t)e, C, priors + (size_t)e * K * (N * N), values + (size_t)e * K, sim_limit,
+                                out);
+}
+
+// oth_puct_reroot_batch in three launches, as oth_puct_reroot: the keep test (it writes no leaves: a fresh
+// board's come with the finish) ...
+template <int N>
+__global__ __launch_bounds__(PUCT_BLOCK) void k_puct_reroot_classify_batch(const uint64_t* __restrict__ boards,
+                                                                           const uint16_t* __restrict__ meta,
+                                                                           const uint64_t* __restrict__ legal, int E,
+                                                                           uint32_t T, uint32_t K,
+                                                                           uint64_t* __restrict__ wsp,
+                                                                           const int32_t* __restrict__ actions) {
+    constexpr int W = Geo<N>::W;
+    const long long e = (long long)blockIdx.x * PUCT_BLOCK + threadIdx.x;
+    const PuctBatchWs<N> bw{PuctWs<N>{wsp, (uint32_t)E, T}, K};
+    if (e >= E || !bw.begun()) return;
+    puct_reroot_classify<N>(bw.plain, (uint32_t)e, boards + (size_t)e * 2 * W, boards + (size_t)e * 2 * W + W,
+                            legal + (size_t)e * W, meta[e], actions[e], PuctLeaves{nullptr, nullptr, nullptr, nullptr});
+}
+
+// ... the compaction, k_puct_reroot_sweep's wave per board ...
+template <int N>
+__global__ __launch_bounds__(64) void k_puct_reroot_sweep_batch(int E, uint32_t T, uint32_t K, uint64_t* wsp) {
+    __shared__ uint32_t fwd[OTH_PUCT_REROOT_LDS];
+    const PuctBatchWs<N> bw{PuctWs<N>{wsp, (uint32_t)E, T}, K};
+    if (!bw.begun()) return;
+    puct_sweep_wave<N>(bw.plain, fwd);
+}
+
+// ... and the new priors, the Select and the leaves on a lane per board
+template <int N>
+__global__ __launch_bounds__(PUCT_BLOCK) void k_puct_reroot_finish_batch(int E, uint32_t T, uint32_t K, int C,
+                                                                         uint64_t* __restrict__ wsp,
+                                                                         const int32_t* __restrict__ root_priors,
+                                                                         uint8_t* __restrict__ kept,
+                                                                         uint32_t sim_limit, PuctLeaves out) {
+    const long long e = (long long)blockIdx.x * PUCT_BLOCK + threadIdx.x;
+    const PuctBatchWs<N> bw{PuctWs<N>{wsp, (uint32_t)E, T}, K};
+    if (e >= E || !bw.begun()) return;
+    puct_reroot_finish_batch<N>(bw, (uint32_t)e, C, root_priors ? root_priors + (size_t)e * (N * N) : nullptr,
+                                kept ? kept + e : nullptr, sim_limit, out);
 }
 
 }  // namespace oth_dev

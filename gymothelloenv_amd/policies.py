@@ -194,11 +194,16 @@ class PUCTPolicy(object):
     of VecOthelloEnv.puct_search, whose leaves `evaluate(leaves) -> (logits, values)`
     judges -- a policy and value network, or one of the evaluators that need none
     (None: playout_evaluator(8, seed), which replays its games move for move).  c is
-    the exploration constant; simulations >= 2 (the first evaluates the root alone)."""
+    the exploration constant; simulations >= 2 (the first evaluates the root alone).
+    leaves_per_board=K > 1 searches with K leaves per launch under virtual loss
+    (puct_search's keyword): about simulations / K calls of evaluate, on K rows."""
 
-    def __init__(self, evaluate=None, simulations=128, c=1.25, seed=0):
+    def __init__(self, evaluate=None, simulations=128, c=1.25, seed=0, leaves_per_board=1):
         self.env = None
         self.simulations, self.c = int(simulations), float(c)
+        self.leaves_per_board = int(leaves_per_board)
+        if not 1 <= self.leaves_per_board <= 64:
+            raise ValueError("leaves_per_board must be in [1, 64]")
         self._seed = int(seed)
         self._own = evaluate is None
         self.evaluate = evaluate
@@ -221,7 +226,8 @@ class PUCTPolicy(object):
         if self.evaluate is None:
             from .vec_env import playout_evaluator
             self.evaluate = playout_evaluator(8, seed=self._seed)
-        a = int(vec.puct_actions(self.evaluate, self.simulations, c=self.c).cpu()[0])
+        kw = dict(leaves_per_board=self.leaves_per_board) if self.leaves_per_board != 1 else {}
+        a = int(vec.puct_actions(self.evaluate, self.simulations, c=self.c, **kw).cpu()[0])
         self.counter += 1
         if a < 0:
             raise ValueError('no possible moves')

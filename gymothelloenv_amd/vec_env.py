@@ -164,6 +164,7 @@ class VecOthelloEnv(object):
         self._mcts_ws = None  # mcts()'s workspace: a uint8 tensor, regrown only when too small
         self._puct_ws = None  # the puct_* search's workspace, its own: mcts() would overwrite a search in progress
         self._puct = None  # the search in progress: (params, the C leaves struct, PuctLeaves)
+        self._puct_k = 0  # its leaves per board in the batch calls; 0: the plain calls began it
         self._region_resets = None  # resets inside an open graph region (None: no region)
 
     # ------------------------------------------------------------------ utils
@@ -679,7 +680,20 @@ class VecOthelloEnv(object):
         ply counter and the tallies are left untouched.  The tree lives in a cached
         workspace of its own (not mcts()'s, whose call would overwrite a search in
         progress), regrown only when too small."""
+        p, lv, leaves = self._puct_setup(1, c, max_tree_nodes, layout, dtype)
+        L.check(self._lib.oth_puct_begin(self._h, ctypes.byref(p), _ptr(self._puct_ws), self._puct_ws.numel(),
+                                         ctypes.byref(lv), self._stream()), "oth_puct_begin")
+        self._puct, self._puct_k = (p, lv, leaves), 0
+        return leaves
+
+    def _puct_setup(self, K, c, max_tree_nodes, layout, dtype, batch=False):
+        """What puct_begin and puct_begin_batch share: the parameters, the workspace (regrown only when
+        too small) and new leaf tensors of E K rows.  The search in progress is dropped."""
         E, nn = self.num_envs, self.board_size * self.board_size
+        K = int(K)
+        if not 1 <= K <= L.OTH_PUCT_MAX_LEAVES:
+            raise ValueError("leaves_per_board must be in [1, %d]" % L.OTH_PUCT_MAX_LEAVES)
+        R = E * K
         if max_tree_nodes is None:
             max_tree_nodes = min(max(nn, 64 * (nn - 4)), L.OTH_PUCT_MAX_TREE_NODES)
         cx = int(round(256 * float(c)))
@@ -693,28 +707,33 @@ class VecOthelloEnv(object):
             lay = _OBS_LAYOUTS.get(layout, -1) if isinstance(layout, str) else int(layout)
             if lay not in _OBS_PLANES or dtype not in _DTYPES:
                 raise ValueError("unknown observation layout %r or dtype %r" % (layout, dtype))
-            obs = torch.empty(self._obs_shape(lay), dtype=dtype, device=self.device)
+            obs = torch.empty((R,) + tuple(self._obs_shape(lay)[1:]), dtype=dtype, device=self.device)
         need = ctypes.c_uint64(0)
-        L.check(self._lib.oth_puct_workspace_bytes(self.board_size, E, p.max_tree_nodes, ctypes.byref(need)),
-                "oth_puct_workspace_bytes")
+        if not batch:
+            L.check(self._lib.oth_puct_workspace_bytes(self.board_size, E, p.max_tree_nodes, ctypes.byref(need)),
+                    "oth_puct_workspace_bytes")
+        else:
+            L.check(self._lib.oth_puct_batch_workspace_bytes(self.board_size, E, p.max_tree_nodes, K,
+                                                             ctypes.byref(need)), "oth_puct_batch_workspace_bytes")
         if self._puct_ws is None or self._puct_ws.numel() < need.value:
             self._puct_ws = None  # (the old one goes first)
             self._puct_ws = torch.empty(need.value, dtype=torch.uint8, device=self.device)
-        leaves = PuctLeaves(self._u8(E), torch.empty(E, 2 * self.words, dtype=torch.int64, device=self.device),
-                            torch.empty(E, dtype=torch.int16, device=self.device),
-                            torch.empty(E, self.words, dtype=torch.int64, device=self.device), obs)
+        leaves = PuctLeaves(self._u8(R), torch.empty(R, 2 * self.words, dtype=torch.int64, device=self.device),
+                            torch.empty(R, dtype=torch.int16, device=self.device),
+                            torch.empty(R, self.words, dtype=torch.int64, device=self.device), obs)
         lv = L.OthPuctLeaves(leaves.kind.data_ptr(), leaves.boards.data_ptr(), leaves.meta.data_ptr(),
                              leaves.legal.data_ptr(), None if obs is None else obs.data_ptr(), lay,
                              _DTYPES[dtype] if obs is not None else 0)
         self._puct = None
-        L.check(self._lib.oth_puct_begin(self._h, ctypes.byref(p), _ptr(self._puct_ws), self._puct_ws.numel(),
-                                         ctypes.byref(lv), self._stream()), "oth_puct_begin")
-        self._puct = (p, lv, leaves)
-        return leaves
+        return p, lv, leaves
 
-    def _puct_state(self):
+    def _puct_state(self, batch=None):
+        """The search in progress; batch False / True: it must be one of the plain / the batch calls."""
         if self._puct is None:
             raise RuntimeError("no search in progress: call puct_begin() first")
+        if batch is not None and batch != (self._puct_k > 0):
+            raise RuntimeError("a search goes on with the calls that began it: this one was begun by %s"
+                               % ("puct_begin_batch()" if self._puct_k > 0 else "puct_begin()"))
         return self._puct
 
     def puct_advance(self, priors, values, more=True):
@@ -726,7 +745,7 @@ class VecOthelloEnv(object):
         descends to its next leaf.  Returns puct_begin's PuctLeaves, rewritten in
         place.  int32 tensors on this device are passed as they are (a captured
         advance reads them again at every replay); others are converted first."""
-        p, lv, leaves = self._puct_state()
+        p, lv, leaves = self._puct_state(False)
         E, nn = self.num_envs, self.board_size * self.board_size
         pr = priors.to(device=self.device, dtype=torch.int32).contiguous()
         vl = values.to(device=self.device, dtype=torch.int32).contiguous()
@@ -770,14 +789,26 @@ class VecOthelloEnv(object):
         max_tree_nodes (None: what `simulations` can reserve at most), layout and
         dtype go to puct_begin, value_sums / best / tree_nodes / status to
         puct_result, whose outputs are returned.  evaluate's floats are the only ones
-        anywhere: given the integers puct_quantize makes of them, the search is exact."""
+        anywhere: given the integers puct_quantize makes of them, the search is exact.
+
+        leaves_per_board=K > 1: the batch calls (puct_begin_batch, puct_advance_batch with
+        sim_limit = simulations), launched until no slot holds a leaf, so evaluate sees E K
+        rows a call and is called about simulations / K times; every searched board ends
+        with exactly `simulations` simulations.  Whether a leaf is left is one small
+        read-back per launch: this path synchronises and refuses a HIP-graph capture."""
         S = int(simulations)
         if S < 1:
             raise ValueError("simulations must be >= 1")
+        K = int(kw.pop("leaves_per_board", 1))
         begin = dict((k, kw.pop(k)) for k in ("c", "max_tree_nodes", "layout", "dtype") if k in kw)
         if begin.get("max_tree_nodes") is None:
             nn = self.board_size * self.board_size
             begin["max_tree_nodes"] = min(max(nn, S * (nn - 4) // 4 + nn), L.OTH_PUCT_MAX_TREE_NODES)
+        if K != 1:
+            _no_capture("puct_search(leaves_per_board > 1)")
+            leaves = self.puct_begin_batch(K, **begin)
+            self._puct_run_batch(evaluate, leaves, S)
+            return self.puct_result(**kw)
         leaves = self.puct_begin(**begin)
         for i in range(S):
             logits, values = evaluate(leaves)
@@ -792,6 +823,77 @@ class VecOthelloEnv(object):
         for k in ("value_sums", "best", "tree_nodes", "status"):
             kw.pop(k, None)
         return self.puct_search(evaluate, simulations, best=True, **kw)[1]
+
+    # ---------------------------------------------- K leaves a board per launch
+    def puct_begin_batch(self, leaves_per_board, c=1.25, max_tree_nodes=None, layout="make_state",
+                         dtype=torch.float32):
+        """puct_begin for a search that emits up to K = leaves_per_board leaves a board per launch
+        under virtual loss (oth_puct_begin_batch; the header defines the merge in integers, one
+        board's slots in ascending order).  The PuctLeaves it returns has E K rows, row e K + j slot
+        j of board e, so any evaluator works unchanged on a batch of E K; a slot without a leaf has
+        kind NONE and shows the root.  Here the root is slot 0's leaf.  The search goes on with
+        puct_advance_batch and puct_reroot_batch; puct_result and puct_pick serve both families."""
+        K = int(leaves_per_board)
+        p, lv, leaves = self._puct_setup(K, c, max_tree_nodes, layout, dtype, batch=True)
+        L.check(self._lib.oth_puct_begin_batch(self._h, ctypes.byref(p), K, _ptr(self._puct_ws),
+                                               self._puct_ws.numel(), ctypes.byref(lv), self._stream()),
+                "oth_puct_begin_batch")
+        self._puct, self._puct_k = (p, lv, leaves), K
+        return leaves
+
+    def puct_advance_batch(self, priors, values, sim_limit=None):
+        """One launch of a batch search (oth_puct_advance_batch): every slot's leaf takes its row of
+        priors int32 (E K, N*N) and values int32 (E K,), in slot order; then each board selects up
+        to K new leaves under virtual loss, none beyond sim_limit simulations at its root in all
+        (None: no limit; 0: none at all, puct_advance's more=False).  A board's batch closes early
+        where a selection meets a leaf already taken in this launch.  Returns the PuctLeaves,
+        rewritten in place."""
+        p, lv, leaves = self._puct_state(True)
+        K = self._puct_k
+        R, nn = self.num_envs * K, self.board_size * self.board_size
+        pr = priors.to(device=self.device, dtype=torch.int32).contiguous()
+        vl = values.to(device=self.device, dtype=torch.int32).contiguous()
+        if pr.numel() != R * nn or vl.numel() != R:
+            raise ValueError("priors must have %d elements and values %d" % (R * nn, R))
+        lim = L.OTH_PUCT_MAX_SIMS if sim_limit is None else int(sim_limit)
+        if not 0 <= lim <= L.OTH_PUCT_MAX_SIMS:
+            raise ValueError("sim_limit is out of range")
+        L.check(self._lib.oth_puct_advance_batch(self._h, ctypes.byref(p), K, _ptr(self._puct_ws),
+                                                 self._puct_ws.numel(), _ptr(pr), _ptr(vl), lim, ctypes.byref(lv),
+                                                 self._stream()), "oth_puct_advance_batch")
+        return leaves
+
+    def puct_reroot_batch(self, actions, root_priors=None, kept=False, sim_limit=None):
+        """puct_reroot for a batch search (oth_puct_reroot_batch): every slot's leaf is dropped, and
+        each searched board selects up to K leaves from its new root, within sim_limit (a kept
+        root's visits count).  A fresh or unexpanded root is slot 0's leaf alone."""
+        p, lv, leaves = self._puct_state(True)
+        K = self._puct_k
+        E, nn = self.num_envs, self.board_size * self.board_size
+        a = actions.to(device=self.device, dtype=torch.int32).contiguous()
+        if a.numel() != E:
+            raise ValueError("expected %d actions, got %d" % (E, a.numel()))
+        rp = None
+        if root_priors is not None:
+            rp = root_priors.to(device=self.device, dtype=torch.int32).contiguous()
+            if rp.numel() != E * nn:
+                raise ValueError("root_priors must have %d elements" % (E * nn))
+        lim = L.OTH_PUCT_MAX_SIMS if sim_limit is None else int(sim_limit)
+        if not 0 <= lim <= L.OTH_PUCT_MAX_SIMS:
+            raise ValueError("sim_limit is out of range")
+        kp = self._u8(E) if kept else None
+        L.check(self._lib.oth_puct_reroot_batch(self._h, ctypes.byref(p), K, _ptr(self._puct_ws),
+                                                self._puct_ws.numel(), _ptr(a), _ptr(rp), _ptr(kp), lim,
+                                                ctypes.byref(lv), self._stream()), "oth_puct_reroot_batch")
+        return (leaves, kp) if kept else leaves
+
+    def _puct_run_batch(self, evaluate, leaves, S):
+        """Launches with sim_limit = S until no slot holds a leaf (one read-back of kind.any() a launch)."""
+        while bool(leaves.kind.any()):
+            logits, values = evaluate(leaves)
+            priors, vals = puct_quantize(logits, leaves.legal, values)
+            leaves = self.puct_advance_batch(priors, vals, sim_limit=S)
+        return leaves
 
     # ------------------------------------------------- self-play on the search's tree
     def puct_pick(self, sample=None, seed=None, counter=None):
@@ -849,7 +951,7 @@ class VecOthelloEnv(object):
         children, the way to mix root noise in again; fresh roots take theirs at
         their first advance.  Returns the search's PuctLeaves, rewritten in place
         with every board's next leaf; with kept=True (the leaves, kept uint8 (E,))."""
-        p, lv, leaves = self._puct_state()
+        p, lv, leaves = self._puct_state(False)
         E, nn = self.num_envs, self.board_size * self.board_size
         a = actions.to(device=self.device, dtype=torch.int32).contiguous()
         if a.numel() != E:
@@ -881,16 +983,35 @@ class VecOthelloEnv(object):
         sudden_death_on_invalid_move, otherwise the turn passes.  Its search begins
         afresh.  max_tree_nodes=None: twice what `simulations` can reserve, since a
         kept subtree comes on top of a move's own expansions; a full tree only stops
-        growing (VALUE leaves)."""
+        growing (VALUE leaves).
+
+        leaves_per_board=K > 1 (among begin_kw): the batch calls, as puct_search runs them,
+        with sim_limit = simulations in every launch and in the re-root; the visits a kept
+        root brings along count, so a move adds what is missing to `simulations`.  This path
+        reads kind.any() back once a launch and refuses a HIP-graph capture."""
         S = int(simulations)
         if S < 1:
             raise ValueError("simulations must be >= 1")
+        K = int(begin_kw.pop("leaves_per_board", 1))
+        if self._puct is not None and max(self._puct_k, 1) != K:
+            raise RuntimeError("the search in progress was begun with leaves_per_board=%d" % max(self._puct_k, 1))
         if self._puct is None:
             if begin_kw.get("max_tree_nodes") is None:
                 nn = self.board_size * self.board_size
                 begin_kw["max_tree_nodes"] = min(max(nn, 2 * (S * (nn - 4) // 4 + nn)), L.OTH_PUCT_MAX_TREE_NODES)
-            self.puct_begin(**begin_kw)
+            if K != 1:
+                self.puct_begin_batch(K, **begin_kw)
+            else:
+                self.puct_begin(**begin_kw)
         leaves = self._puct[2]
+        if K != 1:
+            _no_capture("puct_play(leaves_per_board > 1)")
+            self._puct_run_batch(evaluate, leaves, S)
+            visits = self.puct_result()
+            actions = self.puct_pick(sample)
+            _, rewards, dones, _ = self.step(actions, observe=False)
+            _, kept = self.puct_reroot_batch(actions, kept=True, sim_limit=S)
+            return PuctPlay(actions, visits, rewards, dones, kept)
         for i in range(S):
             logits, values = evaluate(leaves)
             priors, vals = puct_quantize(logits, leaves.legal, values)

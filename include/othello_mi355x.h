@@ -667,6 +667,117 @@ int oth_puct_reroot(oth_env *env, const oth_puct_params *p, void *workspace, uin
                     const int32_t *actions, const int32_t *root_priors, uint8_t *kept,
                     const oth_puct_leaves *leaves, oth_stream_t stream);
 
+/* The batch calls: K leaves a board per launch under virtual loss, so that a
+ * network sees E K rows a call and a move of S simulations needs about S / K
+ * calls.  Virtual loss only needs an order, and one board's K selections have
+ * one by definition -- slot 0, then slot 1, and so on -- so the merge is
+ * defined exactly, in integers, like everything above.  The tree, the nodes,
+ * the key, steps 1 to 3 of oth_puct_advance and struct oth_puct_leaves are
+ * unchanged.
+ *
+ * Shapes.  A board has K slots, j = 0 .. K-1, K in [1, OTH_PUCT_MAX_LEAVES];
+ * row e K + j of every leaf array is slot j of board e: kind uint8[E K], boards
+ * uint64[E K][2W], meta uint16[E K], legal uint64[E K][W]; obs (E K, planes, N,
+ * N) is exactly oth_observe of a handle of E K boards oth_set_state'd to those
+ * three arrays; priors int32[E K][N*N] and values int32[E K] in the same rows.
+ * Every element of every non-NULL array is written by each of the three calls.
+ * A slot without a leaf is written as a board without one is written by the
+ * plain calls: kind OTH_PUCT_LEAF_NONE and the root, with the meta the handle
+ * held at begin or at the last re-root.  E K must fit 31 bits.
+ *
+ * oth_puct_begin_batch is oth_puct_begin: a DONE board's root is the leaf of
+ * slot 0 (EXPAND, or VALUE as there); slots 1 .. K-1 are NONE.
+ *
+ * oth_puct_advance_batch, per board:
+ *  1. Apply.  For j = 0 .. K-1 in ascending order, each slot with a leaf runs
+ *     steps 1 to 3 of oth_puct_advance with that row's priors and value: the
+ *     value, the expansion for kind EXPAND, the backup.  Expansions therefore
+ *     take their child blocks in slot order.  Afterwards no slot holds a leaf.
+ *  2. Select.  sim_limit is in [0, OTH_PUCT_MAX_SIMS]; 0 selects nothing (more
+ *     = 0).  Let r = used (the slots reserved so far) and n_x = 0 for every
+ *     node x (the paths of this launch through x).  For j = 0 .. K-1:
+ *       - the board is closed (below), or the root's v + j >= sim_limit: slot j
+ *         is NONE.
+ *       - otherwise descend from the root exactly as step 4 of oth_puct_advance
+ *         does, with every statistic read through the launch's virtual loss:
+ *           v'_c = v_c + n_c,  w'_c = w_c - OTH_PUCT_VALUE_ONE n_c,
+ *           v'_p = v_p + n_p,
+ *           key = q'_c + floor(C P_c isqrt(2^16 v'_p) / (2^17 (1 + v'_c))),
+ *           q'_c = 0 if v'_c = 0, else floor(w'_c / v'_c) toward minus infinity.
+ *         There is no sign logic: w is already counted for the side that
+ *         chooses among the siblings, and a path in flight is one loss for it.
+ *         The bounds of the plain key hold: v' < 2^24 because of sim_limit,
+ *         |w'| <= 2^15 v', and the numerator stays below 2^52.
+ *       - the descent stops as there: at a terminated node, at a node without
+ *         reserved children, or at a child that is not yet made, which is made
+ *         now.  Let X be the node where it stops.
+ *           X terminated: kind TERMINAL.  Several slots of one launch may hold
+ *             the same terminated node; each is a simulation of its own and no
+ *             evaluation is spent on it.
+ *           X is already the leaf of an earlier slot of this launch (a
+ *             collision): the board is closed for this launch, slot j and all
+ *             later slots are NONE, and path j counts nowhere.
+ *           otherwise, k being X's move count: if r + k <= T, kind EXPAND and
+ *             r += k; else kind VALUE.  Reservations of earlier slots count, so
+ *             every EXPAND leaf still fits when step 1 of the next launch
+ *             applies them in slot order.
+ *       - where slot j got a leaf, n_x += 1 for every node x on its path, the
+ *         root included.
+ *  3. Virtual loss does not survive the launch: when the call returns every
+ *     node holds its real v and w only, and oth_puct_result, oth_puct_pick and
+ *     the re-root's keep test and compaction see the tree the backups made.
+ * A board all of whose slots are NONE ignores priors, values and sim_limit.
+ * A search of S simulations passes sim_limit = S in every call and launches
+ * until no slot holds a leaf: every DONE board then has exactly S, however its
+ * batches closed.
+ *
+ * K = 1.  No virtual loss is ever read and no collision can occur: the call is
+ * oth_puct_advance with more = (the root's v after the backup < sim_limit),
+ * byte for byte in every output -- more = 0 for sim_limit = 0, more = 1 for
+ * sim_limit = OTH_PUCT_MAX_SIMS.  begin_batch is oth_puct_begin, and
+ * reroot_batch is oth_puct_reroot on every board whose new root's v is below
+ * sim_limit (on every board for sim_limit = OTH_PUCT_MAX_SIMS).
+ *
+ * oth_puct_reroot_batch is oth_puct_reroot with steps 1 to 4 and 6 unchanged.
+ * Step 5: every slot's leaf is discarded, and a DONE board runs the Select
+ * above from the new root with sim_limit.  A fresh or unexpanded root is the
+ * leaf of slot 0 alone (slot 1 collides with it).
+ *
+ * Workspace.  At least oth_puct_batch_workspace_bytes(board_size, n_envs, T, K)
+ * bytes, which is never less than oth_puct_workspace_bytes reports, 8-byte
+ * aligned, opaque; it holds one search.  oth_puct_result and oth_puct_pick work
+ * on it unchanged (same handle geometry and T).  A search goes on with the
+ * family that began it: a batch call on a workspace that no begin_batch of the
+ * same geometry, T and K wrote does nothing; a plain advance or reroot on a
+ * batch workspace stays inside the workspace's memory, and what the search does
+ * afterwards is unspecified.  oth_puct_batch_workspace_bytes needs no handle
+ * and no GPU; OTH_EINVAL where oth_puct_workspace_bytes gives it, and for K
+ * outside [1, OTH_PUCT_MAX_LEAVES].
+ *
+ * Handle state, capture and determinism: as the plain calls.  begin_batch and
+ * reroot_batch read boards, meta and the stored possible_moves, advance_batch
+ * only the geometry; none writes anything of the handle.  Each only enqueues
+ * work, is capturable and draws no random number.  Every output is a function
+ * of the board's tree, K, sim_limit and that board's K rows of integers alone,
+ * never of E, the board's index or the mapping to lanes.  The running time is
+ * bounded by K descents of at most N*N + 1 levels (and the re-root's by used).
+ *
+ * OTH_EINVAL, with nothing launched: everything the plain calls refuse, K or
+ * sim_limit out of range (before the handle is looked at), E K above 2^31 - 1,
+ * workspace_bytes below what oth_puct_batch_workspace_bytes reports. */
+#define OTH_PUCT_MAX_LEAVES 64
+int oth_puct_batch_workspace_bytes(int32_t board_size, int32_t n_envs, int32_t max_tree_nodes, int32_t K,
+                                   uint64_t *bytes);
+int oth_puct_begin_batch(oth_env *env, const oth_puct_params *p, int32_t K, void *workspace,
+                         uint64_t workspace_bytes, const oth_puct_leaves *leaves, oth_stream_t stream);
+int oth_puct_advance_batch(oth_env *env, const oth_puct_params *p, int32_t K, void *workspace,
+                           uint64_t workspace_bytes, const int32_t *priors, const int32_t *values,
+                           int32_t sim_limit, const oth_puct_leaves *leaves, oth_stream_t stream);
+int oth_puct_reroot_batch(oth_env *env, const oth_puct_params *p, int32_t K, void *workspace,
+                          uint64_t workspace_bytes, const int32_t *actions, const int32_t *root_priors,
+                          uint8_t *kept, int32_t sim_limit, const oth_puct_leaves *leaves,
+                          oth_stream_t stream);
+
 /* OthelloEnv (othello.py:96-214) for every env: the protagonist's colour per
  * env (protagonist: device int8[E] of +1 white / -1 black, NULL = all white,
  * the reference default) and an embedded opponent played on the device
