@@ -9,6 +9,7 @@ import ctypes
 import numpy as np
 import pytest
 
+import family_cases as fc
 import play_search_ref as pr
 import search_ref as sh
 import solve_ref as sr
@@ -19,6 +20,7 @@ pytestmark = pytest.mark.gpu
 
 FLAG_SETS = {0: {}, 3: dict(sudden_death_on_invalid_move=True, num_disk_as_reward=True), 4: dict(auto_reset=True)}
 PLIES = {4: 6, 6: 8, 8: 8, 10: 6, 16: 3}  # the move-choice run's plies per size
+PLIES.update(fc.PLAY_PLIES)               # (the other sizes run from tests/test_gpu_family_sizes.py)
 
 
 @pytest.fixture(scope="module")

@@ -9,6 +9,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import family_cases as fc
 import mcts_ref as mr
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -75,3 +76,11 @@ def test_key_and_seed_matter(hostlib):
     for kw in (dict(seed=mr.SEED + 1), dict(id_key=mr.ID_KEY + 1), dict(counter=mr.COUNTER + 1),
                dict(id_base=mr.ID_BASE + 1)):
         assert (host_mcts(hostlib, s, I, R, C, T, **kw)[1] != res.wins2).any(), kw
+
+
+@pytest.mark.parametrize("c", [fc.mcts_case(n) for n in fc.NEW_SIZES] + [fc.mcts_case(n, full=True) for n in fc.MCTS_FULL],
+                         ids=lambda c: "n%d-E%d-I%d-R%d-C%d-T%d" % c)
+def test_every_other_size_against_the_reference(hostlib, c):
+    """The board sizes mcts_ref.CASES leaves out: the device's cases of tests/test_gpu_family_sizes.py on the host build."""
+    assert sorted({k[0] for k in mr.CASES} | set(fc.NEW_SIZES)) == fc.ALL_SIZES
+    test_exact_against_the_reference(hostlib, c)

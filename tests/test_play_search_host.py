@@ -11,6 +11,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import family_cases as fc
 import play_search_ref as pr
 import search_ref as sh
 import solve_ref as sr
@@ -162,3 +163,10 @@ def test_signatures_and_struct():
     body = header[header.index("typedef struct oth_search_policy {"):header.index("} oth_search_policy;")]
     assert [ln.split(";")[0].split()[-1].lstrip("*") for ln in body.splitlines()[1:] if ";" in ln] == \
         [f for f, _ in S._fields_]
+
+
+@pytest.mark.parametrize("n", fc.NEW_SIZES_SOLVE)
+def test_every_other_size_equals_the_reference(searchlib, movelib, n):  # noqa: F811
+    """test_equals_the_reference at the board sizes SIZES leaves out."""
+    assert sorted(SIZES + fc.NEW_SIZES_SOLVE) == fc.ALL_SIZES
+    test_equals_the_reference(searchlib, movelib, n)

@@ -10,6 +10,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import family_cases as fc
 import puct_batch_ref as pb
 import puct_ref as pf
 
@@ -202,3 +203,14 @@ def test_families_and_tags(hostlib):
     W = s.W
     lo, hi = 2 + 2 * E, 2 + 2 * E + 3 * W * E + (E + 3) // 4
     assert ((changed >= lo) & (changed < hi)).all()
+
+
+@pytest.mark.parametrize("c", [fc.batch_case(n) for n in fc.NEW_SIZES] + [fc.BATCH_WIDE], ids=lambda c: pb.CASE_ID % c)
+def test_every_other_size_against_the_reference(hostlib, c):
+    """The board sizes puct_batch_ref.CASES leaves out: the device's cases of tests/test_gpu_family_sizes.py on the host
+    build."""
+    assert sorted({k[0] for k in pb.CASES} | set(fc.NEW_SIZES)) == fc.ALL_SIZES
+    s, run, census = fc.batch_run(c)
+    fc.check_batch_case(c, run, census)
+    n, E, sims, C, T, K = c
+    drive(HostSearch(hostlib, s, C, T, K), run, sims, pb.CASE_ID % c)

@@ -9,6 +9,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import family_cases as fc
 import puct_ref as pf
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -122,3 +123,11 @@ def test_the_evaluation_matters(hostlib):
 
     base = visits(0, 0)
     assert (visits(0, 9000) != base).any() and (visits(np.arange(n * n, dtype=np.int32) * 900, 0) != base).any()
+
+
+@pytest.mark.parametrize("c", [fc.puct_case(n) for n in fc.NEW_SIZES] + [fc.puct_case(n, full=True) for n in fc.PUCT_FULL],
+                         ids=lambda c: pf.CASE_ID % c)
+def test_every_other_size_against_the_reference(hostlib, c):
+    """The board sizes puct_ref.CASES leaves out: the device's cases of tests/test_gpu_family_sizes.py on the host build."""
+    assert sorted({k[0] for k in pf.CASES} | set(fc.NEW_SIZES)) == fc.ALL_SIZES
+    test_exact_against_the_reference(hostlib, c)

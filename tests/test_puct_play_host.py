@@ -11,6 +11,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import family_cases as fc
 import puct_play_ref as pp
 import puct_ref as pf
 import test_puct_host as tph
@@ -157,3 +158,14 @@ def test_reroot_to_somewhere_else_is_begin(libs):
             tph.same_leaves(hg.leaves(), ref.leaves[i + 1], "advance %d after the reroot" % i)
         for name, g, w in zip(pf.NAMES, hg.result(), ref.outputs):
             np.testing.assert_array_equal(g, w, err_msg=name)
+
+
+@pytest.mark.parametrize("c", [fc.play_case(n) for n in fc.NEW_SIZES], ids=lambda c: pp.CASE_ID % c)
+def test_every_other_size_against_the_reference(libs, c):
+    """The board sizes puct_play_ref.CASES leaves out: the device's cases of tests/test_gpu_family_sizes.py on the host
+    build."""
+    assert sorted({k[0] for k in pp.CASES} | set(fc.NEW_SIZES)) == fc.ALL_SIZES
+    s, game = pp.case(c)
+    fc.check_play_case(c, game)
+    n, E, S, M, C, T = c
+    play(HostGame(libs, s, C, T), game, c)

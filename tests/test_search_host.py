@@ -9,6 +9,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import family_cases as fc
 import search_ref as sh
 import solve_ref as sr
 
@@ -193,3 +194,15 @@ def test_search_core_under_asan_ubsan(tmp_path):
     r = subprocess.run([exe, str(pos)], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300, env=env)
     assert r.returncode == 0, (r.stdout + r.stderr)[-4000:]
     assert "%d positions clean" % len(lines) in r.stdout
+
+
+@pytest.mark.parametrize("n", fc.NEW_SIZES_SOLVE)
+def test_every_other_size_equals_the_reference(searchlib, n):
+    """The board sizes SIZES leaves out, one weight set (mobility != 0), depths 1 to 3: with them the host build stands
+    in for `nodes` and for the searched moves at all 13 sizes."""
+    assert sorted(SIZES + fc.NEW_SIZES_SOLVE) == fc.ALL_SIZES
+    for depth in fc.SEARCH_DEPTHS:
+        s, res, (w, mob, term) = sh.reference(n, 74, depth, fc.SEARCH_WSET)
+        assert mob != 0
+        assert_equals_reference(host_search(searchlib, s, depth, w, mob, term), res)
+        assert (res.status == sh.DONE).sum() > 30

@@ -9,6 +9,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import family_cases as fc
 import solve_ref as sr
 from oracle import oracle
 from test_bitboard_host import random_boards
@@ -181,3 +182,12 @@ def test_search_core_under_asan_ubsan(tmp_path):
     r = subprocess.run([exe, str(pos)], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300, env=env)
     assert r.returncode == 0, (r.stdout + r.stderr)[-4000:]
     assert "%d positions clean" % len(lines) in r.stdout
+
+
+@pytest.mark.parametrize("n", fc.NEW_SIZES_SOLVE)
+def test_every_other_size_against_the_reference(hostlib, n):
+    """One batch at each board size that the cases above leave out (N = 12 and 13 take three words, 14 and 15 four with
+    a partly used last word, 7, 9 and 11 are odd): with them the host build stands in for `nodes` at all 13 sizes."""
+    s, res, full = sr.batch(n, 37, fc.solve_max_e(n))
+    sr.check_batch(s, res, full)  # the specials are in the batch
+    assert_equals_reference(host_solve(hostlib, s), res)
