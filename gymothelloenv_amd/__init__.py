@@ -20,6 +20,9 @@ terminal/score) as HIP kernels for gfx950 behind a C ABI
     playout_evaluator                search's integers, its leaves, and two evaluators without a network
     PuctPlay                         one move of self-play on that search's tree (VecOthelloEnv.puct_play:
                                      puct_pick, step, puct_reroot)
+    ReplayBatch,                     the replay store of VecOthelloEnv.replay_begin / replay_append /
+    symmetry_masks,                  replay_label / replay_gather / replay_sample: a minibatch, masks under a
+    symmetry_permutations            board symmetry, and the eight square permutations sigma_s
 """
 from ._lib import LIB_PATH, OthelloLibError, load  # noqa: F401
 
@@ -29,7 +32,8 @@ BLACK_DISK, NO_DISK, WHITE_DISK = -1, 0, 1
 def __getattr__(name):
     # lazy: importing the package must not touch the GPU (build() runs on CPU hosts)
     if name in ("VecOthelloEnv", "legal_moves", "default_search_weights", "SearchConfig", "PuctLeaves",
-                "PuctPlay", "puct_quantize", "uniform_evaluator", "playout_evaluator"):
+                "PuctPlay", "puct_quantize", "uniform_evaluator", "playout_evaluator", "ReplayBatch",
+                "symmetry_masks", "symmetry_permutations"):
         from . import vec_env
         return getattr(vec_env, name)
     if name in ("OthelloBaseEnv", "SimpleOthelloEnv", "OthelloEnv"):

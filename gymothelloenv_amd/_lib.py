@@ -50,6 +50,8 @@ OTH_PUCT_VALUE_ONE, OTH_PUCT_PRIOR_MAX, OTH_PUCT_MAX_C = 32768, 65535, 65535  # 
 OTH_PUCT_MAX_TREE_NODES, OTH_PUCT_MAX_SIMS = 1 << 24, (1 << 24) - 1
 OTH_PUCT_LEAF_NONE, OTH_PUCT_LEAF_EXPAND, OTH_PUCT_LEAF_VALUE, OTH_PUCT_LEAF_TERMINAL = range(4)
 OTH_PUCT_MAX_LEAVES = 64  # oth_puct_*_batch
+OTH_REPLAY_MAX_HORIZON, OTH_REPLAY_MAX_ROWS, OTH_REPLAY_MAX_BATCH = 65536, 1 << 24, 1 << 20  # oth_replay_*
+OTH_REPLAY_EMPTY, OTH_REPLAY_OPEN, OTH_REPLAY_LABELLED = range(3)
 OTH_GRAPH_SLOTS = 64
 OTH_GRAPH_COUNTER_SHIFT = 40
 
@@ -117,6 +119,22 @@ class OthPuctLeaves(ctypes.Structure):
                 ("dtype", ctypes.c_int32)]
 
 
+class OthReplayBatch(ctypes.Structure):
+    """struct oth_replay_batch (include/othello_mi355x.h): host memory holding device
+    addresses, each may be NULL."""
+    _fields_ = [("state", ctypes.c_void_p),
+                ("boards", ctypes.c_void_p),
+                ("meta", ctypes.c_void_p),
+                ("legal", ctypes.c_void_p),
+                ("visits", ctypes.c_void_p),
+                ("outcome", ctypes.c_void_p),
+                ("obs", ctypes.c_void_p),
+                ("layout", ctypes.c_int32),
+                ("dtype", ctypes.c_int32),
+                ("rows", ctypes.c_void_p),
+                ("sym", ctypes.c_void_p)]
+
+
 # every symbol include/othello_mi355x.h declares: (restype, argtypes)
 _P = ctypes.c_void_p
 _I32, _U32, _U64, _I64 = ctypes.c_int32, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_int64
@@ -143,6 +161,14 @@ SIGNATURES = {
     "oth_puct_begin_batch": (_I32, [_P, _P, _I32, _P, _U64, _P, _P]),
     "oth_puct_advance_batch": (_I32, [_P, _P, _I32, _P, _U64, _P, _P, _I32, _P, _P]),
     "oth_puct_reroot_batch": (_I32, [_P, _P, _I32, _P, _U64, _P, _P, _P, _I32, _P, _P]),
+    "oth_replay_workspace_bytes": (_I32, [_I32, _I32, _I32, _I32, _P]),
+    "oth_replay_begin": (_I32, [_P, _I32, _I32, _P, _U64, _P]),
+    "oth_replay_append": (_I32, [_P, _I32, _I32, _P, _U64, _P, _P, _P]),
+    "oth_replay_label": (_I32, [_P, _I32, _I32, _P, _U64, _P, _P, _P]),
+    "oth_replay_counts": (_I32, [_P, _I32, _I32, _P, _U64, _P, _P]),
+    "oth_replay_gather": (_I32, [_P, _I32, _I32, _P, _U64, _I32, _P, _P, _P, _P]),
+    "oth_replay_sample": (_I32, [_P, _I32, _I32, _P, _U64, _I32, _I32, _U64, _U32, _U64, _P, _P]),
+    "oth_symmetry_masks": (_I32, [_I32, _I32, _I32, _P, _P, _P, _P]),
     "oth_play_search": (_I32, [_P, _P, _P, _I32, _P, _P, _P, _P, _P]),
     "oth_reset_vs_search": (_I32, [_P, _P, _P, _P, _P]),
     "oth_step_vs_search": (_I32, [_P, _P, _P, _P, _P, _P, _P, _P, _P]),

@@ -7,7 +7,8 @@ fused random-play kernels, its own scheduler flags) once per N = 4..11, csrc/pla
 (oth_playouts), csrc/solve_n.hip (oth_solve), csrc/search_n.hip (oth_search),
 csrc/play_search_n.hip (oth_play_search, oth_reset_vs_search, oth_step_vs_search) and
 csrc/mcts_n.hip (oth_mcts) and csrc/puct_n.hip (oth_puct_begin, oth_puct_advance, oth_puct_result, oth_puct_pick,
-oth_puct_reroot) once per N,
+oth_puct_reroot) and csrc/replay_n.hip (oth_replay_begin, oth_replay_append, oth_replay_label, oth_replay_counts,
+oth_replay_gather, oth_replay_sample, oth_symmetry_masks) once per N,
 csrc/capi.hip holds the C ABI, and the objects are linked into one shared library.
 
 Reproducibility: objects go to a fixed directory (`_objs/`, git-ignored) so the
@@ -32,7 +33,7 @@ SOURCES = ("capi.hip", "kernels_n.hip", "play_rand_n.hip", "masked.hip", "device
            "masked.hpp", "ply.hpp", "sample_step.hpp", "maximin_wave.hpp", "playouts_n.hip", "playouts.hpp",
            "tables.hpp", "state.hpp", "engines.hpp", "policy.hpp", "play.hpp", "vs.hpp", "observe.hpp", "solve_n.hip",
            "solve.hpp", "root_tasks.hpp", "search_n.hip", "search.hpp", "play_search_n.hip", "play_search.hpp",
-           "mcts_n.hip", "mcts.hpp", "puct_n.hip", "puct.hpp")
+           "mcts_n.hip", "mcts.hpp", "puct_n.hip", "puct.hpp", "replay_n.hip", "replay.hpp")
 PLAY_SIZES = list(range(4, 12))  # k_play_rand (one-word boards) and k_play_rand_w (two-word boards)
 # play_rand_n.hip: the max-ILP machine scheduler (one wave per SIMD: latency hidden by the schedule
 # counts, occupancy does not); the rest of the library keeps the default scheduler
@@ -123,6 +124,8 @@ def build(force=False, verbose=True, extra_flags=(), out=OUT, jobs=None, only_si
               for n in SIZES]
     units += [(os.path.join(CSRC, "puct_n.hip"), os.path.join(objdir, "puct_n%d.o" % n), ["-DOTH_N=%d" % n])
               for n in SIZES]
+    units += [(os.path.join(CSRC, "replay_n.hip"), os.path.join(objdir, "replay_n%d.o" % n), ["-DOTH_N=%d" % n])
+              for n in SIZES]
 
     def compile_one(u):
         src, obj, defs = u
@@ -143,7 +146,8 @@ def build(force=False, verbose=True, extra_flags=(), out=OUT, jobs=None, only_si
                                                                                    for n in only_sizes} | {
             "playouts_n%d.o" % n for n in only_sizes} | {"solve_n%d.o" % n for n in only_sizes} | {
             "search_n%d.o" % n for n in only_sizes} | {"play_search_n%d.o" % n for n in only_sizes} | {
-            "mcts_n%d.o" % n for n in only_sizes} | {"puct_n%d.o" % n for n in only_sizes}
+            "mcts_n%d.o" % n for n in only_sizes} | {"puct_n%d.o" % n for n in only_sizes} | {
+            "replay_n%d.o" % n for n in only_sizes}
     if only_sizes is not None or only_units is not None:
         reuse = [os.path.join(OBJDIR, os.path.basename(u[1])) for u in units if os.path.basename(u[1]) not in keep]
         units = [u for u in units if os.path.basename(u[1]) in keep]

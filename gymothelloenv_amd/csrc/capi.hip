@@ -615,6 +615,127 @@ int oth_puct_reroot_batch(oth_env* env, const oth_puct_params* p, int32_t K, voi
     });
 }
 
+int oth_replay_workspace_bytes(int32_t board_size, int32_t n_envs, int32_t horizon, int32_t max_batch,
+                               uint64_t* bytes) {
+    if (!bytes) return fail(OTH_EINVAL, "bytes is NULL");
+    if (board_size < 4 || board_size > 16) return fail(OTH_EINVAL, "board_size must be in [4, 16]");
+    if (n_envs < 1) return fail(OTH_EINVAL, "n_envs must be >= 1");
+    if (horizon < 1 || horizon > OTH_REPLAY_MAX_HORIZON) return fail(OTH_EINVAL, "horizon must be in [1, 65536]");
+    if (max_batch < 1 || max_batch > OTH_REPLAY_MAX_BATCH) return fail(OTH_EINVAL, "max_batch must be in [1, 2^20]");
+    if ((uint64_t)n_envs * (uint64_t)horizon > (uint64_t)OTH_REPLAY_MAX_ROWS)
+        return fail(OTH_EINVAL, "n_envs * horizon must be at most 2^24");
+    *bytes = replay_workspace_words(board_size, (uint64_t)n_envs, (uint64_t)horizon, (uint64_t)max_batch) * 8u;
+    return OTH_OK;
+}
+
+namespace {
+
+// What the oth_replay calls share, in the puct calls' order: what needs no handle to decide first, all of it
+// before the device is touched.  batch: the call's oth_replay_batch, or NULL; n: its rows (1 without one).
+int replay_check(const oth_env* env, int32_t horizon, int32_t max_batch, const void* workspace,
+                 uint64_t workspace_bytes, const oth_replay_batch* batch, int32_t n) {
+    if (!workspace) return fail(OTH_EINVAL, "workspace is NULL");
+    if (horizon < 1 || horizon > OTH_REPLAY_MAX_HORIZON) return fail(OTH_EINVAL, "horizon must be in [1, 65536]");
+    if (max_batch < 1 || max_batch > OTH_REPLAY_MAX_BATCH) return fail(OTH_EINVAL, "max_batch must be in [1, 2^20]");
+    if (n < 1 || n > OTH_REPLAY_MAX_BATCH) return fail(OTH_EINVAL, "n must be in [1, max_batch]");
+    if (reinterpret_cast<uintptr_t>(workspace) & 7u) return fail(OTH_EINVAL, "workspace must be 8-byte aligned");
+    if (batch && batch->obs) {
+        if (batch->layout < OTH_OBS_BOARD || batch->layout > OTH_OBS_LEGAL)
+            return fail(OTH_EINVAL, "unknown layout of the batch's obs");
+        if (batch->dtype < OTH_I8 || batch->dtype > OTH_BF16)
+            return fail(OTH_EINVAL, "unknown dtype of the batch's obs");
+    }
+    if (!env) return fail(OTH_EINVAL, "NULL oth_env");
+    uint64_t need = 0;
+    if (int rc = oth_replay_workspace_bytes(env->n, env->E, horizon, max_batch, &need)) return rc;
+    if (workspace_bytes < need)
+        return fail(OTH_EINVAL, "workspace_bytes is below what oth_replay_workspace_bytes reports");
+    if (n > max_batch) return fail(OTH_EINVAL, "n must be in [1, max_batch]");
+    return OTH_OK;
+}
+
+}  // namespace
+
+int oth_replay_begin(oth_env* env, int32_t horizon, int32_t max_batch, void* workspace, uint64_t workspace_bytes,
+                     oth_stream_t stream) {
+    if (int rc = replay_check(env, horizon, max_batch, workspace, workspace_bytes, nullptr, 1)) return rc;
+    if (int rc = use_device(env)) return rc;
+    return with_n(env->n, [&](auto NC) {
+        return launch_replay_begin<decltype(NC)::value>(env, horizon, max_batch, workspace, (hipStream_t)stream);
+    });
+}
+
+int oth_replay_append(oth_env* env, int32_t horizon, int32_t max_batch, void* workspace, uint64_t workspace_bytes,
+                      const int32_t* visits, const uint8_t* skip, oth_stream_t stream) {
+    if (!visits) return fail(OTH_EINVAL, "visits is NULL");
+    if (int rc = replay_check(env, horizon, max_batch, workspace, workspace_bytes, nullptr, 1)) return rc;
+    if (int rc = use_device(env)) return rc;
+    return with_n(env->n, [&](auto NC) {
+        return launch_replay_append<decltype(NC)::value>(env, horizon, max_batch, workspace, visits, skip,
+                                                         (hipStream_t)stream);
+    });
+}
+
+int oth_replay_label(oth_env* env, int32_t horizon, int32_t max_batch, void* workspace, uint64_t workspace_bytes,
+                     const int32_t* rewards, const uint8_t* dones, oth_stream_t stream) {
+    if (!rewards) return fail(OTH_EINVAL, "rewards is NULL");
+    if (!dones) return fail(OTH_EINVAL, "dones is NULL");
+    if (int rc = replay_check(env, horizon, max_batch, workspace, workspace_bytes, nullptr, 1)) return rc;
+    if (int rc = use_device(env)) return rc;
+    return with_n(env->n, [&](auto NC) {
+        return launch_replay_label<decltype(NC)::value>(env, horizon, max_batch, workspace, rewards, dones,
+                                                        (hipStream_t)stream);
+    });
+}
+
+int oth_replay_counts(oth_env* env, int32_t horizon, int32_t max_batch, void* workspace, uint64_t workspace_bytes,
+                      int64_t* out, oth_stream_t stream) {
+    if (!out) return fail(OTH_EINVAL, "out is NULL");
+    if (int rc = replay_check(env, horizon, max_batch, workspace, workspace_bytes, nullptr, 1)) return rc;
+    if (int rc = use_device(env)) return rc;
+    return with_n(env->n, [&](auto NC) {
+        return launch_replay_counts<decltype(NC)::value>(env, horizon, max_batch, workspace, out, (hipStream_t)stream);
+    });
+}
+
+int oth_replay_gather(oth_env* env, int32_t horizon, int32_t max_batch, void* workspace, uint64_t workspace_bytes,
+                      int32_t n, const int32_t* rows_in, const uint8_t* sym_in, const oth_replay_batch* batch,
+                      oth_stream_t stream) {
+    if (!rows_in) return fail(OTH_EINVAL, "rows_in is NULL");
+    if (!batch) return fail(OTH_EINVAL, "batch is NULL");
+    if (int rc = replay_check(env, horizon, max_batch, workspace, workspace_bytes, batch, n)) return rc;
+    if (int rc = use_device(env)) return rc;
+    return with_n(env->n, [&](auto NC) {
+        return launch_replay_batch<decltype(NC)::value>(env, horizon, max_batch, workspace, n, rows_in, sym_in, 0, 0, 0,
+                                                        0, batch, (hipStream_t)stream);
+    });
+}
+
+int oth_replay_sample(oth_env* env, int32_t horizon, int32_t max_batch, void* workspace, uint64_t workspace_bytes,
+                      int32_t n, int32_t augment, uint64_t seed, uint32_t id_key, uint64_t counter,
+                      const oth_replay_batch* batch, oth_stream_t stream) {
+    if (!batch) return fail(OTH_EINVAL, "batch is NULL");
+    if (int rc = replay_check(env, horizon, max_batch, workspace, workspace_bytes, batch, n)) return rc;
+    if (int rc = use_device(env)) return rc;
+    return with_n(env->n, [&](auto NC) {
+        return launch_replay_batch<decltype(NC)::value>(env, horizon, max_batch, workspace, n, nullptr, nullptr,
+                                                        augment != 0, seed, id_key, counter, batch,
+                                                        (hipStream_t)stream);
+    });
+}
+
+int oth_symmetry_masks(int32_t board_size, int32_t n, int32_t planes, const uint8_t* sym, const uint64_t* in,
+                       uint64_t* out, oth_stream_t stream) {
+    if (!sym || !in || !out) return fail(OTH_EINVAL, "sym, in or out is NULL");
+    if (in == out) return fail(OTH_EINVAL, "in and out must be different arrays");
+    if (n < 1 || planes < 1 || (int64_t)n * planes > INT32_MAX)
+        return fail(OTH_EINVAL, "n and planes must be >= 1 and n * planes at most 2^31 - 1");
+    if (board_size < 4 || board_size > 16) return fail(OTH_EINVAL, "board_size must be in [4, 16]");
+    return with_n(board_size, [&](auto NC) {
+        return launch_symmetry_masks<decltype(NC)::value>(n, planes, sym, in, out, (hipStream_t)stream);
+    });
+}
+
 int oth_search(oth_env* env, int32_t depth, const int8_t* weights, int32_t mobility_weight, int32_t terminal_weight,
                uint64_t max_nodes, int32_t* value, int32_t* best, int32_t* move_values, uint8_t* status,
                uint64_t* nodes, oth_stream_t stream) {

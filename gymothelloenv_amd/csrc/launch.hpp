@@ -186,4 +186,32 @@ constexpr uint64_t puct_batch_workspace_words(int n, uint64_t E, uint64_t T, uin
            (E * K + 3u) / 4u + E * K;
 }
 
+// k_replay_* (oth_replay_*: the self-play samples kept, labelled and drawn) and k_symmetry_masks in
+// replay_n.hip, every N, a unit of its own per board size.  The arguments are checked.  counts and sample
+// are the rank step's two launches first; a non-NULL obs of a batch is one more (launch_observe on the
+// batch's exchange-format arrays, the caller's or the workspace's staging rows).
+template <int N> int launch_replay_begin(oth_env* env, int H, int B, void* workspace, hipStream_t st);
+template <int N>
+int launch_replay_append(oth_env* env, int H, int B, void* workspace, const int32_t* visits, const uint8_t* skip,
+                         hipStream_t st);
+template <int N>
+int launch_replay_label(oth_env* env, int H, int B, void* workspace, const int32_t* rewards, const uint8_t* dones,
+                        hipStream_t st);
+template <int N> int launch_replay_counts(oth_env* env, int H, int B, void* workspace, int64_t* out, hipStream_t st);
+// rows_in NULL: oth_replay_sample (augment, seed, id_key, counter); else oth_replay_gather (rows_in, sym_in)
+template <int N>
+int launch_replay_batch(oth_env* env, int H, int B, void* workspace, int n, const int32_t* rows_in,
+                        const uint8_t* sym_in, int augment, uint64_t seed, uint32_t id_key, uint64_t counter,
+                        const oth_replay_batch* batch, hipStream_t st);
+template <int N>
+int launch_symmetry_masks(int n, int planes, const uint8_t* sym, const uint64_t* in, uint64_t* out, hipStream_t st);
+// the 64-bit words of a store's workspace (replay.hpp ReplayWs): two tags, two header words a board, the rows'
+// state bytes and outcomes, a count word a chunk of 1,024 rows and their prefix, B staging rows in exchange
+// format, then the rows' three boards of W words and their N*N visits
+constexpr uint64_t replay_workspace_words(int n, uint64_t E, uint64_t H, uint64_t B) {
+    return 2u + 2u * E + (E * H + 7u) / 8u + (E * H + 1u) / 2u + (E * H + 1023u) / 1024u +
+           ((E * H + 1023u) / 1024u + 2u) / 2u + (B + 3u) / 4u + 3u * (uint64_t)((n * n + 63) / 64) * B +
+           3u * (uint64_t)((n * n + 63) / 64) * E * H + (E * H * (uint64_t)(n * n) + 1u) / 2u;
+}
+
 }  // namespace oth_host

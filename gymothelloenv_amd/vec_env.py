@@ -48,6 +48,9 @@ def _ptr(t):
 PuctLeaves = collections.namedtuple("PuctLeaves", ("kind", "boards", "meta", "legal", "obs"))
 # one move of self-play on the search's tree (VecOthelloEnv.puct_play)
 PuctPlay = collections.namedtuple("PuctPlay", ("actions", "visits", "rewards", "dones", "kept"))
+# a minibatch of the replay store (VecOthelloEnv.replay_gather / replay_sample)
+ReplayBatch = collections.namedtuple("ReplayBatch", ("state", "boards", "meta", "legal", "visits", "outcome", "obs",
+                                                     "rows", "sym"))
 
 
 def puct_quantize(logits, leaf_legal, values):
@@ -165,6 +168,9 @@ class VecOthelloEnv(object):
         self._puct_ws = None  # the puct_* search's workspace, its own: mcts() would overwrite a search in progress
         self._puct = None  # the search in progress: (params, the C leaves struct, PuctLeaves)
         self._puct_k = 0  # its leaves per board in the batch calls; 0: the plain calls began it
+        self._replay_ws = None  # the replay store's workspace, regrown only when too small
+        self._replay = None  # the store in use: (horizon, max_batch)
+        self._replay_calls = 0  # `counter` of the next replay_sample() call that gives none
         self._region_resets = None  # resets inside an open graph region (None: no region)
 
     # ------------------------------------------------------------------ utils
@@ -988,8 +994,13 @@ class VecOthelloEnv(object):
         leaves_per_board=K > 1 (among begin_kw): the batch calls, as puct_search runs them,
         with sim_limit = simulations in every launch and in the re-root; the visits a kept
         root brings along count, so a move adds what is missing to `simulations`.  This path
-        reads kind.any() back once a launch and refuses a HIP-graph capture."""
+        reads kind.any() back once a launch and refuses a HIP-graph capture.
+
+        record=True (a keyword beside begin_kw, default False): the move goes into the
+        replay store (replay_begin first): replay_append(visits) before the step,
+        replay_label(rewards, dones) after it."""
         S = int(simulations)
+        record = bool(begin_kw.pop("record", False))
         if S < 1:
             raise ValueError("simulations must be >= 1")
         K = int(begin_kw.pop("leaves_per_board", 1))
@@ -1009,7 +1020,11 @@ class VecOthelloEnv(object):
             self._puct_run_batch(evaluate, leaves, S)
             visits = self.puct_result()
             actions = self.puct_pick(sample)
+            if record:
+                self.replay_append(visits)
             _, rewards, dones, _ = self.step(actions, observe=False)
+            if record:
+                self.replay_label(rewards, dones)
             _, kept = self.puct_reroot_batch(actions, kept=True, sim_limit=S)
             return PuctPlay(actions, visits, rewards, dones, kept)
         for i in range(S):
@@ -1018,9 +1033,155 @@ class VecOthelloEnv(object):
             leaves = self.puct_advance(priors, vals, more=i < S - 1)
         visits = self.puct_result()
         actions = self.puct_pick(sample)
+        if record:
+            self.replay_append(visits)
         _, rewards, dones, _ = self.step(actions, observe=False)
+        if record:
+            self.replay_label(rewards, dones)
         _, kept = self.puct_reroot(actions, kept=True)
         return PuctPlay(actions, visits, rewards, dones, kept)
+
+    # ------------------------------------------------------------ the replay store
+    def replay_begin(self, horizon, max_batch=4096):
+        """Begin an empty replay store for this env's boards (oth_replay_begin;
+        include/othello_mi355x.h defines every call in integers): a ring of `horizon`
+        record slots per board, row e * horizon + j being slot j of board e, and
+        batches of at most `max_batch` rows.  The store lives in a cached workspace
+        of its own, regrown only when too small."""
+        H, B = int(horizon), int(max_batch)
+        need = ctypes.c_uint64(0)
+        L.check(self._lib.oth_replay_workspace_bytes(self.board_size, self.num_envs, H, B, ctypes.byref(need)),
+                "oth_replay_workspace_bytes")
+        if self._replay_ws is None or self._replay_ws.numel() < need.value:
+            self._replay_ws = None  # (the old one goes first)
+            self._replay_ws = torch.empty(need.value, dtype=torch.uint8, device=self.device)
+        L.check(self._lib.oth_replay_begin(self._h, H, B, _ptr(self._replay_ws), self._replay_ws.numel(),
+                                           self._stream()), "oth_replay_begin")
+        self._replay = (H, B)
+
+    def _replay_args(self):
+        if self._replay is None:
+            raise RuntimeError("no replay store: call replay_begin() first")
+        H, B = self._replay
+        return self._h, H, B, _ptr(self._replay_ws), self._replay_ws.numel()
+
+    def replay_append(self, visits, skip=None):
+        """Record every live board's position with its visit target (oth_replay_append):
+        visits int32 (E, N*N), cleaned to [0, 2^24 - 1] on the stored possible moves and
+        0 elsewhere; a board records unless it is terminated, skip[e] (uint8 / bool (E,))
+        is set or no cleaned visit is positive.  Call it before the step that plays the
+        move.  int32 tensors on this device are passed as they are."""
+        E, nn = self.num_envs, self.board_size * self.board_size
+        v = visits.to(device=self.device, dtype=torch.int32).contiguous()
+        if v.numel() != E * nn:
+            raise ValueError("visits must have %d elements" % (E * nn))
+        sk = None
+        if skip is not None:
+            sk = skip.to(device=self.device).ne(0).to(torch.uint8).contiguous()
+            if sk.numel() != E:
+                raise ValueError("skip must have %d elements" % E)
+        L.check(self._lib.oth_replay_append(*self._replay_args(), _ptr(v), _ptr(sk), self._stream()),
+                "oth_replay_append")
+
+    def replay_label(self, rewards, dones):
+        """Label the finished games (oth_replay_label): where dones[e] is set, every open
+        record of board e's current game takes the outcome +rewards[e] (clamped to
+        [-32768, 32768]) if its side to move is the side that moved at the latest
+        append, else -rewards[e].  rewards and dones are what step() returned for the
+        ply played from the latest appended position."""
+        E = self.num_envs
+        r = rewards.to(device=self.device, dtype=torch.int32).contiguous()
+        d = dones.to(device=self.device)
+        d = (d if d.dtype == torch.uint8 else d.ne(0).to(torch.uint8)).contiguous()
+        if r.numel() != E or d.numel() != E:
+            raise ValueError("rewards and dones must have %d elements" % E)
+        L.check(self._lib.oth_replay_label(*self._replay_args(), _ptr(r), _ptr(d), self._stream()),
+                "oth_replay_label")
+
+    def replay_counts(self):
+        """int64 (3,) on this device: the rows that are empty, open and labelled (oth_replay_counts)."""
+        out = torch.empty(3, dtype=torch.int64, device=self.device)
+        L.check(self._lib.oth_replay_counts(*self._replay_args(), _ptr(out), self._stream()), "oth_replay_counts")
+        return out
+
+    def _replay_batch(self, n, layout, dtype, fields):
+        """New tensors of n rows for a batch, and its C struct.  fields None: all of them."""
+        W, nn, dev = self.words, self.board_size * self.board_size, self.device
+        want = ReplayBatch._fields if fields is None else tuple(fields)
+        unknown = set(want) - set(ReplayBatch._fields)
+        if unknown:
+            raise ValueError("unknown batch fields %s" % sorted(unknown))
+        obs, lay = None, 0
+        if layout is not None and "obs" in want:
+            lay = _OBS_LAYOUTS.get(layout, -1) if isinstance(layout, str) else int(layout)
+            if lay not in _OBS_PLANES or dtype not in _DTYPES:
+                raise ValueError("unknown observation layout %r or dtype %r" % (layout, dtype))
+            obs = torch.empty((n,) + tuple(self._obs_shape(lay)[1:]), dtype=dtype, device=dev)
+        shapes = dict(state=((n,), torch.uint8), boards=((n, 2 * W), torch.int64), meta=((n,), torch.int16),
+                      legal=((n, W), torch.int64), visits=((n, nn), torch.int32), outcome=((n,), torch.int32),
+                      rows=((n,), torch.int32), sym=((n,), torch.uint8))
+        t = {k: torch.empty(sh, dtype=dt, device=dev) if k in want else None for k, (sh, dt) in shapes.items()}
+        batch = ReplayBatch(t["state"], t["boards"], t["meta"], t["legal"], t["visits"], t["outcome"], obs, t["rows"],
+                            t["sym"])
+        ptr = lambda x: None if x is None else x.data_ptr()  # noqa: E731
+        c = L.OthReplayBatch(ptr(batch.state), ptr(batch.boards), ptr(batch.meta), ptr(batch.legal), ptr(batch.visits),
+                             ptr(batch.outcome), ptr(obs), lay, _DTYPES[dtype] if obs is not None else 0,
+                             ptr(batch.rows), ptr(batch.sym))
+        return batch, c
+
+    def replay_gather(self, rows, sym=None, layout="make_state", dtype=torch.float32, fields=None):
+        """The store's rows `rows` (int32 (n,), n <= max_batch) under the symmetries `sym`
+        (uint8 (n,), the low three bits; None: the identity) as a ReplayBatch of tensors
+        on this device (oth_replay_gather): state uint8 (n,), boards int64 (n, 2W), meta
+        int16 (n,), legal int64 (n, W) in the exchange format, visits int32 (n, N*N),
+        outcome int32 (n,) from the row's mover's side, obs = observe(layout, dtype) of
+        those positions (layout=None: none), and rows / sym as used (-1: a row number
+        outside the store, which gives an empty row: zeros).  fields: the names to make
+        (the others are None and cost nothing)."""
+        r = rows.to(device=self.device, dtype=torch.int32).contiguous()
+        n = r.numel()
+        sm = None
+        if sym is not None:
+            sm = sym.to(device=self.device, dtype=torch.uint8).contiguous()
+            if sm.numel() != n:
+                raise ValueError("sym must have %d elements" % n)
+        batch, c = self._replay_batch(n, layout, dtype, fields)
+        L.check(self._lib.oth_replay_gather(*self._replay_args(), n, _ptr(r), _ptr(sm), ctypes.byref(c),
+                                            self._stream()), "oth_replay_gather")
+        return batch
+
+    def replay_sample(self, n, augment=True, seed=None, counter=None, id_key=0, layout="make_state",
+                      dtype=torch.float32, fields=None):
+        """A minibatch of n labelled rows drawn uniformly with replacement, each under a
+        random symmetry of the board when augment is set (oth_replay_sample): a
+        stateless Philox draw keyed by (seed, id_key + i, counter) that depends on this
+        store alone.  seed=None: the env's seed XOR PLAYOUT_SEED_XOR; counter=None:
+        `replay_sample_counter`, which then moves on by one.  A store without a
+        labelled row gives empty rows (rows -1).  Returns replay_gather's ReplayBatch."""
+        n = int(n)
+        key = (self.seed ^ PLAYOUT_SEED_XOR if seed is None else int(seed)) & (2 ** 64 - 1)
+        own = counter is None
+        ctr = self._replay_calls if own else int(counter)
+        if not 0 <= ctr < 2 ** 64:
+            raise ValueError("counter is out of range")
+        if n < 1:
+            raise ValueError("n must be >= 1")
+        batch, c = self._replay_batch(n, layout, dtype, fields)
+        L.check(self._lib.oth_replay_sample(*self._replay_args(), n, int(bool(augment)), key,
+                                            int(id_key) & 0xFFFFFFFF, ctr, ctypes.byref(c), self._stream()),
+                "oth_replay_sample")
+        if own:
+            self._replay_calls += 1
+        return batch
+
+    @property
+    def replay_sample_counter(self):
+        """`counter` of the next replay_sample() call that does not give one."""
+        return self._replay_calls
+
+    @replay_sample_counter.setter
+    def replay_sample_counter(self, v):
+        self._replay_calls = int(v)
 
     # ------------------------------------------------------------ exact endgame
     def solve(self, max_empties=10, max_nodes=1 << 22, best=False, move_values=False, status=False, nodes=False):
@@ -1410,4 +1571,44 @@ def legal_moves(board_size, mover, opponent):
     stream = ctypes.c_void_p(torch.cuda.current_stream(mover.device).cuda_stream)
     L.check(lib.oth_legal_moves(int(board_size), int(mover.shape[0]), _ptr(mover), _ptr(opponent), _ptr(out),
                                 stream), "oth_legal_moves")
+    return out
+
+
+def symmetry_masks(board_size, sym, masks):
+    """Stateless oth_symmetry_masks: masks int64 (n, planes, W) or (n, W) on a GPU, each
+    row's planes under the board symmetry sym[i] & 7 (uint8 (n,)): bit sigma_s(a) of the
+    result is bit a of the input (symmetry_permutations has sigma)."""
+    lib = L.load()
+    m = masks.contiguous()
+    n = int(m.shape[0])
+    planes = int(m.numel() // (n * nwords(max(4, int(board_size))))) if n else 0
+    sm = sym.to(device=m.device, dtype=torch.uint8).contiguous()
+    if sm.numel() != n:
+        raise ValueError("sym must have %d elements" % n)
+    out = torch.empty_like(m)
+    stream = ctypes.c_void_p(torch.cuda.current_stream(m.device).cuda_stream)
+    with torch.cuda.device(m.device):
+        L.check(lib.oth_symmetry_masks(int(board_size), n, planes, _ptr(sm), _ptr(m), _ptr(out), stream),
+                "oth_symmetry_masks")
+    return out
+
+
+def symmetry_permutations(n):
+    """int64 (8, N*N) on the host: [s][a] = sigma_s(a), the square that square a = (r, c)
+    goes to under symmetry s of the replay store -- (r, c) transposed if s & 1, then the
+    row mirrored if s & 2, then the column if s & 4.  For visits v of a position and
+    logits l of its image under s: v_image[sigma[s]] = v, and l[sigma[s]] maps the
+    network's logits back to the position's own squares."""
+    n = int(n)
+    out = torch.empty(8, n * n, dtype=torch.int64)
+    for s in range(8):
+        for a in range(n * n):
+            r, c = divmod(a, n)
+            if s & 1:
+                r, c = c, r
+            if s & 2:
+                r = n - 1 - r
+            if s & 4:
+                c = n - 1 - c
+            out[s, a] = r * n + c
     return out

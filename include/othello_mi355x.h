@@ -778,6 +778,149 @@ int oth_puct_reroot_batch(oth_env *env, const oth_puct_params *p, int32_t K, voi
                           uint8_t *kept, int32_t sim_limit, const oth_puct_leaves *leaves,
                           oth_stream_t stream);
 
+/* The replay store: the self-play samples kept, labelled and drawn on the
+ * device (no reference counterpart: the training side of the AlphaZero loop).
+ * A learner trains on the triple (position, visit target, outcome from the
+ * mover's side), drawn as random minibatches under the eight symmetries of the
+ * board.  The store keeps, for each of the E boards of a handle geometry, a
+ * ring of H record slots in a workspace the caller supplies; every output is
+ * an exact integer function of the inputs, and the mapping to lanes shows in
+ * none of them.
+ *
+ * Geometry and workspace.  Every call names the store's geometry: the
+ * handle's (N, E), `horizon` H in [1, OTH_REPLAY_MAX_HORIZON] with E H <=
+ * OTH_REPLAY_MAX_ROWS, and `max_batch` B in [1, OTH_REPLAY_MAX_BATCH], the
+ * most rows one gather or sample writes.  The workspace is device memory of at
+ * least oth_replay_workspace_bytes(board_size, n_envs, H, B) bytes, 8-byte
+ * aligned and opaque.  It needs no initialising before oth_replay_begin and
+ * holds no addresses, so a byte copy of it is a checkpoint of the store.
+ * Every other replay call on a workspace that no oth_replay_begin of the same
+ * geometry (N, E, H, B) wrote does nothing.  oth_replay_workspace_bytes needs
+ * no handle and no GPU; OTH_EINVAL as oth_puct_workspace_bytes gives it, and
+ * for H, B or E H out of range.
+ *
+ * Row e H + j is slot j of board e.  A row holds a state (OTH_REPLAY_EMPTY,
+ * _OPEN or _LABELLED), black[W], white[W], legal[W], the turn bit, visits
+ * int32[N*N] and an outcome int32.  Per board the store also keeps count (the
+ * records made; count mod H is the next slot), span in [0, H] (the current
+ * game's records still in the ring) and last_turn.
+ *
+ * oth_replay_begin.  Every row becomes EMPTY, count and span become 0.  The
+ * call reads only the handle's geometry.
+ *
+ * oth_replay_append.  visits int32[E][N*N] is required; skip uint8[E] may be
+ * NULL.  The call reads the handle's boards, meta and stored possible_moves
+ * and writes nothing of the handle.  Per board, last_turn = meta bit 0,
+ * always.  The cleaned visits are c[a] = clamp(visits[a], 0, 2^24 - 1) where a
+ * is in the stored mask (restricted to the board), else 0.  The board records
+ * iff it is not terminated, skip is NULL or skip[e] = 0, and the sum of c is
+ * positive.  Recording: slot j = count mod H is overwritten, whatever its
+ * state; the row takes the discs, the stored mask, the turn bit and c; its
+ * state becomes OPEN and its outcome 0; count += 1; span = min(span + 1, H).
+ * A board that does not record changes nothing but last_turn.  A game with
+ * more than H records loses its oldest OPEN rows to its newest.
+ *
+ * oth_replay_label.  rewards int32[E] and dones uint8[E] are required; the
+ * call reads only the geometry.  Per board with dones[e] != 0: z =
+ * clamp(rewards[e], -32768, 32768); every OPEN row among the board's last span
+ * records becomes LABELLED with outcome +z if the row's turn bit equals
+ * last_turn, else -z; span becomes 0.  Boards with dones[e] = 0 are untouched.
+ * The caller's side of the contract: rewards[e] is the result for the side
+ * that was to move at the board's latest append -- exactly what oth_step
+ * reports for the ply played from that position, with and without
+ * OTH_DISK_REWARD, on the sudden-death path and with OTH_AUTO_RESET (the
+ * handle is not read); oth_step_vs' reward is the protagonist's, who is that
+ * side too.
+ *
+ * oth_replay_counts.  out, device int64[3]: the rows in state EMPTY, OPEN and
+ * LABELLED.
+ *
+ * Batches (struct oth_replay_batch, host memory holding device pointers; any
+ * pointer may be NULL; every element of every non-NULL array is written), n
+ * rows: state uint8[n], boards uint64[n][2W], meta uint16[n], legal
+ * uint64[n][W], visits int32[n][N*N], outcome int32[n], obs of `layout` and
+ * `dtype`, rows int32[n], sym uint8[n].
+ *
+ * Symmetry s in [0, 8).  For stored square a = (r, c): (r1, c1) = (c, r) if
+ * s & 1, else (r, c); r2 = N - 1 - r1 if s & 2, else r1; c2 = N - 1 - c1 if
+ * s & 4, else c1; sigma_s(a) = r2 N + c2: the eight elements of the square's
+ * symmetry group.  Row i of a batch built from store row rho under s: bit
+ * sigma_s(a) of black, white and legal is bit a of the stored words (squares
+ * off the board are dropped); visits[sigma_s(a)] is the stored visits[a]; meta
+ * is the turn bit alone (no terminated bit, no winner, no opening plies);
+ * outcome and state are as stored; obs is exactly what oth_observe(layout,
+ * dtype) gives for a handle of n boards oth_set_state'd to those three arrays,
+ * (n, planes, N, N).  An EMPTY row gives zeros everywhere, with state 0.
+ *
+ * oth_replay_gather.  rows_in int32[n] (required) and sym_in uint8[n] (NULL:
+ * all 0) are device inputs, n in [1, B].  Row i is store row rows_in[i] under
+ * sym_in[i] & 7; a row number outside [0, E H) gives the EMPTY row.
+ * batch->rows and batch->sym echo what was used, with -1 for an out-of-range
+ * row.  This is the dump the tests read the store through, and how a caller
+ * with priorities of its own draws.
+ *
+ * oth_replay_sample.  M being the number of LABELLED rows, for i in [0, n):
+ * (u0, u1) are words 0 and 1 of the Philox4x32-10 block of key `seed` and
+ * counter words (id_key + i mod 2^32, counter lo, counter hi, purpose 5) -- a
+ * purpose of its own beside the five of the draws above; r = floor(u0 M /
+ * 2^32); the row is the (r + 1)-th LABELLED row in ascending row number; s =
+ * u1 >> 29 if augment != 0, else 0; then as gather.  M = 0 gives every row
+ * EMPTY and rows -1.  Any 64-bit counter is accepted and is baked into the
+ * launch (a captured sample replays the same draw on whatever the store then
+ * holds).  The draw depends on this store alone, not on env_id_base: a sharded
+ * run does not repeat an unsharded one.
+ *
+ * oth_symmetry_masks is stateless, like oth_legal_moves: in and out are device
+ * uint64[n][planes][W], sym uint8[n]; every plane of row i is transformed by
+ * sym[i] & 7.  in == out is OTH_EINVAL.
+ *
+ * Handle state and capture.  Only append reads the handle's boards; none of
+ * the calls writes anything of the handle.  Each only enqueues work, never
+ * synchronises the host and is capturable into a HIP graph.  append and label
+ * bake nothing in, so a captured self-play move replays correctly.
+ *
+ * OTH_EINVAL, with nothing launched: NULL required pointers (workspace,
+ * visits, rewards, dones, out, batch, rows_in; sym, in, out of
+ * oth_symmetry_masks), n, H or B out of range, a misaligned workspace, an
+ * unknown layout or dtype beside a non-NULL obs (all these before the handle is
+ * looked at), a NULL handle, E H above OTH_REPLAY_MAX_ROWS, workspace_bytes
+ * below what oth_replay_workspace_bytes reports, n above B.  Every board size
+ * works. */
+#define OTH_REPLAY_MAX_HORIZON 65536
+#define OTH_REPLAY_MAX_ROWS    (1 << 24)
+#define OTH_REPLAY_MAX_BATCH   (1 << 20)
+enum { OTH_REPLAY_EMPTY = 0, OTH_REPLAY_OPEN = 1, OTH_REPLAY_LABELLED = 2 };
+typedef struct oth_replay_batch {
+    uint8_t  *state;    /* [n] OTH_REPLAY_* */
+    uint64_t *boards;   /* [n][2W] */
+    uint16_t *meta;     /* [n] */
+    uint64_t *legal;    /* [n][W] */
+    int32_t  *visits;   /* [n][N*N] */
+    int32_t  *outcome;  /* [n] */
+    void     *obs;      /* (n, planes, N, N) of layout and dtype, as oth_observe */
+    int32_t   layout, dtype;
+    int32_t  *rows;     /* [n] the store row used, -1: none */
+    uint8_t  *sym;      /* [n] the symmetry used */
+} oth_replay_batch;
+int oth_replay_workspace_bytes(int32_t board_size, int32_t n_envs, int32_t horizon, int32_t max_batch,
+                               uint64_t *bytes);
+int oth_replay_begin(oth_env *env, int32_t horizon, int32_t max_batch, void *workspace, uint64_t workspace_bytes,
+                     oth_stream_t stream);
+int oth_replay_append(oth_env *env, int32_t horizon, int32_t max_batch, void *workspace, uint64_t workspace_bytes,
+                      const int32_t *visits, const uint8_t *skip, oth_stream_t stream);
+int oth_replay_label(oth_env *env, int32_t horizon, int32_t max_batch, void *workspace, uint64_t workspace_bytes,
+                     const int32_t *rewards, const uint8_t *dones, oth_stream_t stream);
+int oth_replay_counts(oth_env *env, int32_t horizon, int32_t max_batch, void *workspace, uint64_t workspace_bytes,
+                      int64_t *out, oth_stream_t stream);
+int oth_replay_gather(oth_env *env, int32_t horizon, int32_t max_batch, void *workspace, uint64_t workspace_bytes,
+                      int32_t n, const int32_t *rows_in, const uint8_t *sym_in, const oth_replay_batch *batch,
+                      oth_stream_t stream);
+int oth_replay_sample(oth_env *env, int32_t horizon, int32_t max_batch, void *workspace, uint64_t workspace_bytes,
+                      int32_t n, int32_t augment, uint64_t seed, uint32_t id_key, uint64_t counter,
+                      const oth_replay_batch *batch, oth_stream_t stream);
+int oth_symmetry_masks(int32_t board_size, int32_t n, int32_t planes, const uint8_t *sym, const uint64_t *in,
+                       uint64_t *out, oth_stream_t stream);
+
 /* OthelloEnv (othello.py:96-214) for every env: the protagonist's colour per
  * env (protagonist: device int8[E] of +1 white / -1 black, NULL = all white,
  * the reference default) and an embedded opponent played on the device
