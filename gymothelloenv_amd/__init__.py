@@ -23,6 +23,8 @@ terminal/score) as HIP kernels for gfx950 behind a C ABI
     ReplayBatch,                     the replay store of VecOthelloEnv.replay_begin / replay_append /
     symmetry_masks,                  replay_label / replay_gather / replay_sample: a minibatch, masks under a
     symmetry_permutations            board symmetry, and the eight square permutations sigma_s
+    DeviceNet, MLPPolicyValue,       the int8 policy-value network evaluated on the device (oth_net_eval): an
+    net_features                     evaluator without a float, the float module a learner trains, its inputs
 """
 from ._lib import LIB_PATH, OthelloLibError, load  # noqa: F401
 
@@ -36,6 +38,9 @@ def __getattr__(name):
                 "symmetry_masks", "symmetry_permutations"):
         from . import vec_env
         return getattr(vec_env, name)
+    if name in ("DeviceNet", "MLPPolicyValue", "net_features"):
+        from . import net
+        return getattr(net, name)
     if name in ("OthelloBaseEnv", "SimpleOthelloEnv", "OthelloEnv"):
         from . import othello
         return getattr(othello, name)

@@ -52,6 +52,8 @@ OTH_PUCT_LEAF_NONE, OTH_PUCT_LEAF_EXPAND, OTH_PUCT_LEAF_VALUE, OTH_PUCT_LEAF_TER
 OTH_PUCT_MAX_LEAVES = 64  # oth_puct_*_batch
 OTH_REPLAY_MAX_HORIZON, OTH_REPLAY_MAX_ROWS, OTH_REPLAY_MAX_BATCH = 65536, 1 << 24, 1 << 20  # oth_replay_*
 OTH_REPLAY_EMPTY, OTH_REPLAY_OPEN, OTH_REPLAY_LABELLED = range(3)
+OTH_NET_MAX_LAYERS, OTH_NET_MAX_WIDTH, OTH_NET_MAX_SHIFT = 4, 512, 24  # oth_net_*
+OTH_NET_BIAS_MAX, OTH_NET_MAX_ROWS = 1 << 30, 1 << 24
 OTH_GRAPH_SLOTS = 64
 OTH_GRAPH_COUNTER_SHIFT = 40
 
@@ -135,6 +137,15 @@ class OthReplayBatch(ctypes.Structure):
                 ("sym", ctypes.c_void_p)]
 
 
+class OthNetParams(ctypes.Structure):
+    """struct oth_net_params (include/othello_mi355x.h): host memory read during the call."""
+    _fields_ = [("layers", ctypes.c_int32),
+                ("width", ctypes.c_int32),
+                ("shift", ctypes.c_int32 * 4),
+                ("policy_shift", ctypes.c_int32),
+                ("value_shift", ctypes.c_int32)]
+
+
 # every symbol include/othello_mi355x.h declares: (restype, argtypes)
 _P = ctypes.c_void_p
 _I32, _U32, _U64, _I64 = ctypes.c_int32, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_int64
@@ -169,6 +180,9 @@ SIGNATURES = {
     "oth_replay_gather": (_I32, [_P, _I32, _I32, _P, _U64, _I32, _P, _P, _P, _P]),
     "oth_replay_sample": (_I32, [_P, _I32, _I32, _P, _U64, _I32, _I32, _U64, _U32, _U64, _P, _P]),
     "oth_symmetry_masks": (_I32, [_I32, _I32, _I32, _P, _P, _P, _P]),
+    "oth_net_blob_bytes": (_I32, [_I32, _P, _P]),
+    "oth_net_pack": (_I32, [_I32, _P, _P, _P, _P, _U64]),
+    "oth_net_eval": (_I32, [_I32, _I32, _P, _P, _U64, _P, _P, _P, _P, _P, _P, _P]),
     "oth_play_search": (_I32, [_P, _P, _P, _I32, _P, _P, _P, _P, _P]),
     "oth_reset_vs_search": (_I32, [_P, _P, _P, _P, _P]),
     "oth_step_vs_search": (_I32, [_P, _P, _P, _P, _P, _P, _P, _P, _P]),

@@ -11,6 +11,7 @@
 #include <type_traits>
 
 #include "launch.hpp"
+#include "net.hpp"
 
 using namespace oth;
 using namespace oth_host;
@@ -734,6 +735,57 @@ int oth_symmetry_masks(int32_t board_size, int32_t n, int32_t planes, const uint
     return with_n(board_size, [&](auto NC) {
         return launch_symmetry_masks<decltype(NC)::value>(n, planes, sym, in, out, (hipStream_t)stream);
     });
+}
+
+namespace {
+// oth_net_params as net.hpp's NetParams, checked: what every oth_net call does first
+int net_params(int32_t board_size, const oth_net_params* params, NetParams* out) {
+    if (!params) return fail(OTH_EINVAL, "params is NULL");
+    out->layers = params->layers;
+    out->width = params->width;
+    for (int l = 0; l < 4; ++l) out->shift[l] = params->shift[l];
+    out->policy_shift = params->policy_shift;
+    out->value_shift = params->value_shift;
+    if (const char* why = net_check(board_size, out)) return fail(OTH_EINVAL, why);
+    return OTH_OK;
+}
+}  // namespace
+
+int oth_net_blob_bytes(int32_t board_size, const oth_net_params* params, uint64_t* bytes) {
+    if (!bytes) return fail(OTH_EINVAL, "bytes is NULL");
+    NetParams np;
+    if (int rc = net_params(board_size, params, &np)) return rc;
+    *bytes = net_geo(board_size, np).bytes();
+    return OTH_OK;
+}
+
+int oth_net_pack(int32_t board_size, const oth_net_params* params, const int8_t* w, const int32_t* b, void* blob,
+                 uint64_t blob_bytes) {
+    if (!w || !b || !blob) return fail(OTH_EINVAL, "w, b or blob is NULL");
+    NetParams np;
+    if (int rc = net_params(board_size, params, &np)) return rc;
+    if (reinterpret_cast<uintptr_t>(blob) & 15u) return fail(OTH_EINVAL, "blob must be 16-byte aligned");
+    if (blob_bytes < net_geo(board_size, np).bytes())
+        return fail(OTH_EINVAL, "blob_bytes is below what oth_net_blob_bytes reports");
+    if (const char* why = net_pack(board_size, np, w, b, reinterpret_cast<uint8_t*>(blob))) return fail(OTH_EINVAL, why);
+    return OTH_OK;
+}
+
+int oth_net_eval(int32_t board_size, int32_t n_rows, const oth_net_params* params, const void* blob,
+                 uint64_t blob_bytes, const uint64_t* boards, const uint16_t* meta, const uint64_t* legal,
+                 int32_t* priors, int32_t* values, int32_t* logits, oth_stream_t stream) {
+    if (!blob) return fail(OTH_EINVAL, "blob is NULL");
+    if (!boards || !meta || !legal) return fail(OTH_EINVAL, "boards, meta or legal is NULL");
+    if (!priors || !values) return fail(OTH_EINVAL, "priors or values is NULL");
+    NetParams np;
+    if (int rc = net_params(board_size, params, &np)) return rc;
+    if (n_rows < 0 || n_rows > OTH_NET_MAX_ROWS) return fail(OTH_EINVAL, "n_rows must be in [0, 2^24]");
+    if (reinterpret_cast<uintptr_t>(blob) & 15u) return fail(OTH_EINVAL, "blob must be 16-byte aligned");
+    if (blob_bytes < net_geo(board_size, np).bytes())
+        return fail(OTH_EINVAL, "blob_bytes is below what oth_net_blob_bytes reports");
+    if (n_rows == 0) return OTH_OK;
+    return launch_net_eval(board_size, params, n_rows, blob, boards, meta, legal, priors, values, logits,
+                           (hipStream_t)stream);
 }
 
 int oth_search(oth_env* env, int32_t depth, const int8_t* weights, int32_t mobility_weight, int32_t terminal_weight,

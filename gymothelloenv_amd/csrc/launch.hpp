@@ -214,4 +214,10 @@ constexpr uint64_t replay_workspace_words(int n, uint64_t E, uint64_t H, uint64_
            3u * (uint64_t)((n * n + 63) / 64) * E * H + (E * H * (uint64_t)(n * n) + 1u) / 2u;
 }
 
+// k_net_eval (oth_net_eval: the int8 policy-value network on n_rows >= 1 rows in exchange format) in net.hip, one
+// unit for every board size.  The arguments are checked.
+int launch_net_eval(int n, const oth_net_params* p, int n_rows, const void* blob, const uint64_t* boards,
+                    const uint16_t* meta, const uint64_t* legal, int32_t* priors, int32_t* values, int32_t* logits,
+                    hipStream_t st);
+
 }  // namespace oth_host

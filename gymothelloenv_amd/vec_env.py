@@ -75,6 +75,16 @@ def puct_quantize(logits, leaf_legal, values):
     return priors, torch.round(v * float(L.OTH_PUCT_VALUE_ONE)).to(torch.int32)
 
 
+def _puct_evaluate(evaluate, leaves):
+    """What puct_search, puct_play and the batch loop give to the advance: evaluate's
+    (logits, values) quantised by puct_quantize, or, from an evaluator whose
+    `quantized` attribute is true (net.DeviceNet), its (priors, values) as they are."""
+    out, values = evaluate(leaves)
+    if getattr(evaluate, "quantized", False):
+        return out, values
+    return puct_quantize(out, leaves.legal, values)
+
+
 def _leaves_board_size(leaves):
     if leaves.obs is None:
         raise ValueError("this evaluator takes the board size from leaves.obs: begin the search with a layout")
@@ -796,6 +806,9 @@ class VecOthelloEnv(object):
         dtype go to puct_begin, value_sums / best / tree_nodes / status to
         puct_result, whose outputs are returned.  evaluate's floats are the only ones
         anywhere: given the integers puct_quantize makes of them, the search is exact.
+        An evaluator whose `quantized` attribute is true (net.DeviceNet) returns the
+        advance's (priors, values) itself and puct_quantize is not called: then there
+        is no float at all, and layout=None saves the observation.
 
         leaves_per_board=K > 1: the batch calls (puct_begin_batch, puct_advance_batch with
         sim_limit = simulations), launched until no slot holds a leaf, so evaluate sees E K
@@ -817,8 +830,7 @@ class VecOthelloEnv(object):
             return self.puct_result(**kw)
         leaves = self.puct_begin(**begin)
         for i in range(S):
-            logits, values = evaluate(leaves)
-            priors, vals = puct_quantize(logits, leaves.legal, values)
+            priors, vals = _puct_evaluate(evaluate, leaves)
             leaves = self.puct_advance(priors, vals, more=i < S - 1)
         return self.puct_result(**kw)
 
@@ -896,8 +908,7 @@ class VecOthelloEnv(object):
     def _puct_run_batch(self, evaluate, leaves, S):
         """Launches with sim_limit = S until no slot holds a leaf (one read-back of kind.any() a launch)."""
         while bool(leaves.kind.any()):
-            logits, values = evaluate(leaves)
-            priors, vals = puct_quantize(logits, leaves.legal, values)
+            priors, vals = _puct_evaluate(evaluate, leaves)
             leaves = self.puct_advance_batch(priors, vals, sim_limit=S)
         return leaves
 
@@ -1028,8 +1039,7 @@ class VecOthelloEnv(object):
             _, kept = self.puct_reroot_batch(actions, kept=True, sim_limit=S)
             return PuctPlay(actions, visits, rewards, dones, kept)
         for i in range(S):
-            logits, values = evaluate(leaves)
-            priors, vals = puct_quantize(logits, leaves.legal, values)
+            priors, vals = _puct_evaluate(evaluate, leaves)
             leaves = self.puct_advance(priors, vals, more=i < S - 1)
         visits = self.puct_result()
         actions = self.puct_pick(sample)

@@ -921,6 +921,90 @@ int oth_replay_sample(oth_env *env, int32_t horizon, int32_t max_batch, void *wo
 int oth_symmetry_masks(int32_t board_size, int32_t n, int32_t planes, const uint8_t *sym, const uint64_t *in,
                        uint64_t *out, oth_stream_t stream);
 
+/* The network: an int8 policy-value MLP evaluated on rows in the exchange
+ * format, one launch for any number of rows (no reference counterpart: the
+ * evaluator of the AlphaZero loop).  Its outputs are exactly the `priors` and
+ * `values` that oth_puct_advance and oth_puct_advance_batch take, and every one
+ * of them is an exact integer function of the row, the parameters and the weight
+ * bytes: no float is involved.  The calls are stateless and take no handle.
+ *
+ * Geometry.  N is the board size, nn = N N, W the words of a board.  There are
+ * F = 3 nn input features, L hidden layers (1 <= L <= OTH_NET_MAX_LAYERS), all of
+ * one width H, a multiple of 64 in [64, OTH_NET_MAX_WIDTH], and a head of nn + 1
+ * rows: nn policy rows and one value row.
+ *
+ * Parameters (struct oth_net_params, host memory read during the call, named in
+ * every call): layers = L, width = H, shift[l] for layer l < L (the others are
+ * not read), policy_shift and value_shift; every shift read is in [0, 24].
+ *
+ * Logical weights (oth_net_pack's host inputs).  w: int8, w[0] [H][F], then
+ * w[l] [H][H] for 1 <= l < L, then the head wh [nn + 1][H], one after the other.
+ * b: int32, b[l] [H] for l < L, then bh [nn + 1].  Every bias satisfies |b| <=
+ * 2^30 = OTH_NET_BIAS_MAX.  With that bound no accumulator leaves int32: the
+ * first layer is at most 768 * 128 + 2^30 in magnitude (768 = 3 * 256 features of
+ * 0 or 1), every later layer and the head at most 512 * 127 * 128 + 2^30 (512
+ * inputs in [0, 127]).
+ *
+ * One row is boards uint64[2W] (black words, then white), meta uint16 and legal
+ * uint64[W].  The mover's words are the white words if meta bit 0 is set, else
+ * the black words; the other colour's are the opponent's.  For a < nn: x[a] is
+ * the mover's bit a, x[nn + a] the opponent's bit a, x[2 nn + a] bit a of legal.
+ * Bits at or above nn and every other meta bit are never read; the kind of a
+ * leaf is not an input.
+ *   h_0 = x.  For l < L: acc = b[l][j] + sum_i w[l][j][i] h_l[i], and
+ *   h_{l+1}[j] = min(127, max(0, acc >> shift[l])), an arithmetic shift.
+ *   z[o] = bh[o] + sum_j wh[o][j] h_L[j], o = 0 .. nn.
+ *   value = clamp(z[nn] >> value_shift, -32768, 32768).
+ *
+ * Priors.  M is the set of squares a < nn whose legal bit is set.  If M is
+ * empty every prior is 0.  Otherwise m = max over M of z[a]; d = (m - z[a]) >>
+ * policy_shift with the difference taken in 64 bits; i = d >> 8, f = d & 255;
+ * e_a = 0 if i >= 31, else EXP2[f] >> i; S = sum over M of e_a, an int64 (S >=
+ * 2^30: the maximum contributes EXP2[0]); prior[a] = floor((65535 e_a + floor(S
+ * / 2)) / S) for a in M and 0 outside M.  EXP2[f] = round(2^30 2^(-f / 256)), the
+ * 256 literal constants of csrc/net.hpp (EXP2[0] = 1073741824, EXP2[1] =
+ * 1070838486, EXP2[255] = 538326517; no entry is nearer than 0.0054 to a
+ * rounding tie).  This is round(65535 softmax over the legal squares) with
+ * logits in units of 2^-(8 + policy_shift) octaves; the value is in units of
+ * 2^-15 = 1 / OTH_PUCT_VALUE_ONE.
+ *
+ * oth_net_blob_bytes: the size of the packed weights.  Needs no GPU.
+ * oth_net_pack: host memory to host memory; validates every range above and
+ * writes the device layout of the weights into blob (blob_bytes at least what
+ * oth_net_blob_bytes reports, blob 16-byte aligned).  The layout is the library's
+ * and opaque; it holds no addresses, so a byte copy to the device is all that is
+ * needed, and it depends on (board_size, params): an evaluation that names
+ * another geometry or other shifts than the blob was packed for writes nothing.
+ * oth_net_eval: boards uint64[R][2W], meta uint16[R], legal uint64[R][W] and blob
+ * are device inputs, R = n_rows in [0, OTH_NET_MAX_ROWS]; priors int32[R][nn] and
+ * values int32[R] are written; logits int32[R][nn + 1] (z, for tests) may be
+ * NULL.  Rows are independent of each other and of how they are batched.  The
+ * call only enqueues work (one launch; none for R = 0), never synchronises and
+ * is capturable into a HIP graph.
+ *
+ * OTH_EINVAL, with nothing launched or written: NULL pointers (all but logits), a
+ * board size, a field of params or a bias out of range, blob_bytes below what
+ * oth_net_blob_bytes reports, a blob that is not 16-byte aligned, n_rows outside
+ * [0, OTH_NET_MAX_ROWS]. */
+#define OTH_NET_MAX_LAYERS 4
+#define OTH_NET_MAX_WIDTH  512
+#define OTH_NET_MAX_SHIFT  24
+#define OTH_NET_BIAS_MAX   (1 << 30)
+#define OTH_NET_MAX_ROWS   (1 << 24)
+typedef struct oth_net_params {
+    int32_t layers;       /* L in [1, 4] */
+    int32_t width;        /* H: a multiple of 64 in [64, 512] */
+    int32_t shift[4];     /* shift[l], l < L, in [0, 24] */
+    int32_t policy_shift; /* in [0, 24] */
+    int32_t value_shift;  /* in [0, 24] */
+} oth_net_params;
+int oth_net_blob_bytes(int32_t board_size, const oth_net_params *params, uint64_t *bytes);
+int oth_net_pack(int32_t board_size, const oth_net_params *params, const int8_t *w, const int32_t *b, void *blob,
+                 uint64_t blob_bytes);
+int oth_net_eval(int32_t board_size, int32_t n_rows, const oth_net_params *params, const void *blob,
+                 uint64_t blob_bytes, const uint64_t *boards, const uint16_t *meta, const uint64_t *legal,
+                 int32_t *priors, int32_t *values, int32_t *logits, oth_stream_t stream);
+
 /* OthelloEnv (othello.py:96-214) for every env: the protagonist's colour per
  * env (protagonist: device int8[E] of +1 white / -1 black, NULL = all white,
  * the reference default) and an embedded opponent played on the device
