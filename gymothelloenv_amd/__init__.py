@@ -25,6 +25,8 @@ terminal/score) as HIP kernels for gfx950 behind a C ABI
     symmetry_permutations            board symmetry, and the eight square permutations sigma_s
     DeviceNet, MLPPolicyValue,       the int8 policy-value network evaluated on the device (oth_net_eval): an
     net_features                     evaluator without a float, the float module a learner trains, its inputs
+    RootNoise, dirichlet_table       Dirichlet root noise for self-play, drawn on the device in integers
+                                     (VecOthelloEnv.puct_noise; puct_search / puct_play take noise=RootNoise(...))
 """
 from ._lib import LIB_PATH, OthelloLibError, load  # noqa: F401
 
@@ -41,6 +43,9 @@ def __getattr__(name):
     if name in ("DeviceNet", "MLPPolicyValue", "net_features"):
         from . import net
         return getattr(net, name)
+    if name in ("RootNoise", "dirichlet_table"):
+        from . import noise
+        return getattr(noise, name)
     if name in ("OthelloBaseEnv", "SimpleOthelloEnv", "OthelloEnv"):
         from . import othello
         return getattr(othello, name)

@@ -50,6 +50,7 @@ OTH_PUCT_VALUE_ONE, OTH_PUCT_PRIOR_MAX, OTH_PUCT_MAX_C = 32768, 65535, 65535  # 
 OTH_PUCT_MAX_TREE_NODES, OTH_PUCT_MAX_SIMS = 1 << 24, (1 << 24) - 1
 OTH_PUCT_LEAF_NONE, OTH_PUCT_LEAF_EXPAND, OTH_PUCT_LEAF_VALUE, OTH_PUCT_LEAF_TERMINAL = range(4)
 OTH_PUCT_MAX_LEAVES = 64  # oth_puct_*_batch
+OTH_NOISE_TABLE, OTH_NOISE_G_MAX = 4096, 1 << 24  # oth_puct_noise
 OTH_REPLAY_MAX_HORIZON, OTH_REPLAY_MAX_ROWS, OTH_REPLAY_MAX_BATCH = 65536, 1 << 24, 1 << 20  # oth_replay_*
 OTH_REPLAY_EMPTY, OTH_REPLAY_OPEN, OTH_REPLAY_LABELLED = range(3)
 OTH_NET_MAX_LAYERS, OTH_NET_MAX_WIDTH, OTH_NET_MAX_SHIFT = 4, 512, 24  # oth_net_*
@@ -168,6 +169,7 @@ SIGNATURES = {
     "oth_puct_result": (_I32, [_P, _P, _P, _U64, _P, _P, _P, _P, _P, _P]),
     "oth_puct_pick": (_I32, [_P, _P, _P, _U64, _P, _U64, _U32, _U64, _P, _P]),
     "oth_puct_reroot": (_I32, [_P, _P, _P, _U64, _P, _P, _P, _P, _P]),
+    "oth_puct_noise": (_I32, [_P, _I32, _P, _P, _P, _P, _I32, _P, _U64, _U32, _U64, _P]),
     "oth_puct_batch_workspace_bytes": (_I32, [_I32, _I32, _I32, _I32, _P]),
     "oth_puct_begin_batch": (_I32, [_P, _P, _I32, _P, _U64, _P, _P]),
     "oth_puct_advance_batch": (_I32, [_P, _P, _I32, _P, _U64, _P, _P, _I32, _P, _P]),

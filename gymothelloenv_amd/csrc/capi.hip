@@ -788,6 +788,23 @@ int oth_net_eval(int32_t board_size, int32_t n_rows, const oth_net_params* param
                            (hipStream_t)stream);
 }
 
+int oth_puct_noise(oth_env* env, int32_t rows_per_board, const uint8_t* kind, const uint64_t* boards,
+                   const int32_t* priors_in, int32_t* priors_out, int32_t epsilon, const uint32_t* table, uint64_t seed,
+                   uint32_t id_key, uint64_t counter, oth_stream_t stream) {
+    // what needs no handle to decide first, all of it before the device is touched
+    if (!priors_in || !priors_out) return fail(OTH_EINVAL, "priors_in or priors_out is NULL");
+    if (!table) return fail(OTH_EINVAL, "table is NULL");
+    if ((kind == nullptr) != (boards == nullptr)) return fail(OTH_EINVAL, "kind and boards go together: both or neither");
+    if (rows_per_board < 1 || rows_per_board > OTH_PUCT_MAX_LEAVES)
+        return fail(OTH_EINVAL, "rows_per_board must be in [1, 64]");
+    if (epsilon < 0 || epsilon > 256) return fail(OTH_EINVAL, "epsilon must be in [0, 256]");
+    if (!env) return fail(OTH_EINVAL, "NULL oth_env");
+    if ((int64_t)env->E * rows_per_board > INT32_MAX) return fail(OTH_EINVAL, "n_envs * rows_per_board must fit 31 bits");
+    if (int rc = use_device(env)) return rc;
+    return launch_puct_noise(env, rows_per_board, kind, boards, priors_in, priors_out, epsilon, table, seed, id_key,
+                             counter, (hipStream_t)stream);
+}
+
 int oth_search(oth_env* env, int32_t depth, const int8_t* weights, int32_t mobility_weight, int32_t terminal_weight,
                uint64_t max_nodes, int32_t* value, int32_t* best, int32_t* move_values, uint8_t* status,
                uint64_t* nodes, oth_stream_t stream) {

@@ -220,4 +220,10 @@ int launch_net_eval(int n, const oth_net_params* p, int n_rows, const void* blob
                     const uint16_t* meta, const uint64_t* legal, int32_t* priors, int32_t* values, int32_t* logits,
                     hipStream_t st);
 
+// k_puct_noise (oth_puct_noise: Dirichlet root noise mixed into rows of priors) in noise.hip, one unit for every
+// board size.  The arguments are checked.
+int launch_puct_noise(oth_env* env, int rows_per_board, const uint8_t* kind, const uint64_t* boards,
+                      const int32_t* priors_in, int32_t* priors_out, int epsilon, const uint32_t* table, uint64_t seed,
+                      uint32_t id_key, uint64_t counter, hipStream_t st);
+
 }  // namespace oth_host

@@ -174,6 +174,7 @@ class VecOthelloEnv(object):
         self._sample_calls = 0  # Philox counter of sample_actions
         self._playout_calls = 0  # `counter` of the next playouts() call that gives none
         self._pick_calls = 0  # `counter` of the next sampling puct_pick() call that gives none
+        self._noise_calls = 0  # `counter` of the next puct_noise() call that gives none
         self._mcts_ws = None  # mcts()'s workspace: a uint8 tensor, regrown only when too small
         self._puct_ws = None  # the puct_* search's workspace, its own: mcts() would overwrite a search in progress
         self._puct = None  # the search in progress: (params, the C leaves struct, PuctLeaves)
@@ -814,11 +815,17 @@ class VecOthelloEnv(object):
         sim_limit = simulations), launched until no slot holds a leaf, so evaluate sees E K
         rows a call and is called about simulations / K times; every searched board ends
         with exactly `simulations` simulations.  Whether a leaf is left is one small
-        read-back per launch: this path synchronises and refuses a HIP-graph capture."""
+        read-back per launch: this path synchronises and refuses a HIP-graph capture.
+
+        noise=RootNoise(...) (a keyword, default None): Dirichlet root noise, drawn on the
+        device in integers -- the priors of the first advance go through puct_noise in
+        leaf mode, which reaches exactly the boards whose pending leaf is the root.
+        Without the keyword not one launch is added."""
         S = int(simulations)
         if S < 1:
             raise ValueError("simulations must be >= 1")
         K = int(kw.pop("leaves_per_board", 1))
+        noise = kw.pop("noise", None)
         begin = dict((k, kw.pop(k)) for k in ("c", "max_tree_nodes", "layout", "dtype") if k in kw)
         if begin.get("max_tree_nodes") is None:
             nn = self.board_size * self.board_size
@@ -826,11 +833,13 @@ class VecOthelloEnv(object):
         if K != 1:
             _no_capture("puct_search(leaves_per_board > 1)")
             leaves = self.puct_begin_batch(K, **begin)
-            self._puct_run_batch(evaluate, leaves, S)
+            self._puct_run_batch(evaluate, leaves, S, noise)
             return self.puct_result(**kw)
         leaves = self.puct_begin(**begin)
         for i in range(S):
             priors, vals = _puct_evaluate(evaluate, leaves)
+            if i == 0 and noise is not None:
+                priors = self._puct_leaf_noise(noise, priors, leaves, 1)
             leaves = self.puct_advance(priors, vals, more=i < S - 1)
         return self.puct_result(**kw)
 
@@ -905,10 +914,15 @@ class VecOthelloEnv(object):
                                                 ctypes.byref(lv), self._stream()), "oth_puct_reroot_batch")
         return (leaves, kp) if kept else leaves
 
-    def _puct_run_batch(self, evaluate, leaves, S):
-        """Launches with sim_limit = S until no slot holds a leaf (one read-back of kind.any() a launch)."""
+    def _puct_run_batch(self, evaluate, leaves, S, noise=None):
+        """Launches with sim_limit = S until no slot holds a leaf (one read-back of kind.any() a launch).
+        noise: root noise on the first launch's priors, where a slot 0 holds the root."""
+        first = True
         while bool(leaves.kind.any()):
             priors, vals = _puct_evaluate(evaluate, leaves)
+            if first and noise is not None:
+                priors = self._puct_leaf_noise(noise, priors, leaves, self._puct_k)
+            first = False
             leaves = self.puct_advance_batch(priors, vals, sim_limit=S)
         return leaves
 
@@ -953,6 +967,94 @@ class VecOthelloEnv(object):
     @puct_pick_counter.setter
     def puct_pick_counter(self, v):
         self._pick_calls = int(v)
+
+    # ------------------------------------------------------------- root noise
+    def puct_noise(self, priors, epsilon, table, leaves=None, rows_per_board=1, out=None, seed=None, id_key=0,
+                   counter=None):
+        """Dirichlet root noise mixed into rows of priors, in integers (oth_puct_noise;
+        the header defines the draw and the mix).  priors int32 (E K, N*N), K =
+        rows_per_board; epsilon an int in [0, 256], in units of 1/256; table int32
+        (4096,), noise.dirichlet_table's.  Row e K of board e becomes ((256 - epsilon)
+        clamp(p, 0, 65535) + epsilon eta + 128) >> 8 on the squares of the handle's
+        possible_moves, eta the normalised table draws of those squares; every other
+        row and square is copied.
+
+        leaves None ("root mode"): every board takes noise -- for the root_priors of
+        puct_reroot, from an evaluation of the handle's position.  leaves a PuctLeaves
+        ("leaf mode"): only where the leaf of row e K is an EXPAND leaf on the handle's
+        own board, that is, where the pending leaf is the root -- for the priors of the
+        first advance of a move.
+
+        out None: a new tensor; out a contiguous int32 tensor on this device of the
+        same size (it may be `priors` itself: in place).  The draws are keyed by (seed,
+        global env id + id_key, counter, square): a sharded run equals the unsharded
+        one.  seed=None: the env's seed XOR PLAYOUT_SEED_XOR; counter=None:
+        `puct_noise_counter`, which then moves on by one.  The call reads the handle
+        and a search's leaves, writes neither, and is capturable with the counter
+        baked in."""
+        E, nn = self.num_envs, self.board_size * self.board_size
+        K = int(rows_per_board)
+        if not 1 <= K <= L.OTH_PUCT_MAX_LEAVES:
+            raise ValueError("rows_per_board must be in [1, %d]" % L.OTH_PUCT_MAX_LEAVES)
+        eps = int(epsilon)
+        if not 0 <= eps <= 256:
+            raise ValueError("epsilon must be an integer in [0, 256] (units of 1/256)")
+        pr = priors.to(device=self.device, dtype=torch.int32).contiguous()
+        if pr.numel() != E * K * nn:
+            raise ValueError("priors must have %d elements" % (E * K * nn))
+        tb = table.to(device=self.device, dtype=torch.int32).contiguous()
+        if tb.numel() != L.OTH_NOISE_TABLE:
+            raise ValueError("table must have %d entries" % L.OTH_NOISE_TABLE)
+        if out is None:
+            out = torch.empty_like(pr)
+        elif not isinstance(out, torch.Tensor) or out.dtype != torch.int32 or out.device != self.device or \
+                not out.is_contiguous() or out.numel() != pr.numel():
+            raise ValueError("out must be a contiguous int32 tensor of %d elements on %s" % (pr.numel(), self.device))
+        kind = boards = None
+        if leaves is not None:
+            kind, boards = leaves.kind, leaves.boards
+            if kind.dtype != torch.uint8 or boards.dtype != torch.int64 or kind.device != self.device or \
+                    boards.device != self.device or not kind.is_contiguous() or not boards.is_contiguous() or \
+                    kind.numel() != E * K or boards.numel() != E * K * 2 * self.words:
+                raise ValueError("leaves must be a PuctLeaves of %d rows on %s" % (E * K, self.device))
+        key = (self.seed ^ PLAYOUT_SEED_XOR if seed is None else int(seed)) & (2 ** 64 - 1)
+        own = counter is None
+        ctr = self._noise_calls if own else int(counter)
+        if not 0 <= ctr < 2 ** 64:
+            raise ValueError("counter is out of range")
+        L.check(self._lib.oth_puct_noise(self._h, K, _ptr(kind), _ptr(boards), _ptr(pr), _ptr(out), eps, _ptr(tb), key,
+                                         int(id_key) & 0xffffffff, ctr, self._stream()), "oth_puct_noise")
+        if own:
+            self._noise_calls += 1
+        return out
+
+    @property
+    def puct_noise_counter(self):
+        """`counter` of the next puct_noise() call that does not give one."""
+        return self._noise_calls
+
+    @puct_noise_counter.setter
+    def puct_noise_counter(self, v):
+        self._noise_calls = int(v)
+
+    def _puct_leaf_noise(self, noise, priors, leaves, K):
+        """A move's first advance under `noise` (a noise.RootNoise): the leaf-mode call on the evaluator's
+        priors, in place where they are the int32 rows the advance takes."""
+        own = priors.dtype == torch.int32 and priors.device == self.device and priors.is_contiguous()
+        return self.puct_noise(priors, noise.epsilon, noise.table_on(self.device), leaves=leaves, rows_per_board=K,
+                               out=priors if own else None)
+
+    def _puct_root_noise(self, noise, evaluate):
+        """puct_play's root_priors under `noise`: one more evaluation, of the stepped handle's position (its
+        get_state rows as a PuctLeaves, with the observation of the search's layout where it has one), through
+        the root-mode call."""
+        _, lv, leaves = self._puct_state()
+        boards, meta, legal = self.get_state()
+        obs = None if leaves.obs is None else self.observe(int(lv.layout), leaves.obs.dtype)
+        kind = torch.full((self.num_envs,), L.OTH_PUCT_LEAF_EXPAND, dtype=torch.uint8, device=self.device)
+        priors, _ = _puct_evaluate(evaluate, PuctLeaves(kind, boards, meta, legal, obs))
+        own = priors.dtype == torch.int32 and priors.device == self.device and priors.is_contiguous()
+        return self.puct_noise(priors, noise.epsilon, noise.table_on(self.device), out=priors if own else None)
 
     def puct_reroot(self, actions, root_priors=None, kept=False):
         """Carry the search to the position the handle has reached since it began --
@@ -1009,9 +1111,20 @@ class VecOthelloEnv(object):
 
         record=True (a keyword beside begin_kw, default False): the move goes into the
         replay store (replay_begin first): replay_append(visits) before the step,
-        replay_label(rewards, dones) after it."""
+        replay_label(rewards, dones) after it.
+
+        noise=RootNoise(...) (a keyword beside begin_kw, default None): Dirichlet root
+        noise on every move's root, in integers on the device.  The priors of the
+        call's first advance go through puct_noise in leaf mode (fresh roots and kept
+        roots that are not expanded yet; other leaves are untouched); after the step
+        the evaluator runs once more, on the stepped handle's position (get_state's
+        rows as a PuctLeaves, with the observation of the search's layout where it has
+        one), its priors go through puct_noise in root mode and are the re-root's
+        root_priors, so a kept root's children take noise too.  puct_noise_counter moves
+        on by one a call.  Without the keyword not one launch is added."""
         S = int(simulations)
         record = bool(begin_kw.pop("record", False))
+        noise = begin_kw.pop("noise", None)
         if S < 1:
             raise ValueError("simulations must be >= 1")
         K = int(begin_kw.pop("leaves_per_board", 1))
@@ -1028,7 +1141,7 @@ class VecOthelloEnv(object):
         leaves = self._puct[2]
         if K != 1:
             _no_capture("puct_play(leaves_per_board > 1)")
-            self._puct_run_batch(evaluate, leaves, S)
+            self._puct_run_batch(evaluate, leaves, S, noise)
             visits = self.puct_result()
             actions = self.puct_pick(sample)
             if record:
@@ -1036,10 +1149,13 @@ class VecOthelloEnv(object):
             _, rewards, dones, _ = self.step(actions, observe=False)
             if record:
                 self.replay_label(rewards, dones)
-            _, kept = self.puct_reroot_batch(actions, kept=True, sim_limit=S)
+            rp = None if noise is None else self._puct_root_noise(noise, evaluate)
+            _, kept = self.puct_reroot_batch(actions, root_priors=rp, kept=True, sim_limit=S)
             return PuctPlay(actions, visits, rewards, dones, kept)
         for i in range(S):
             priors, vals = _puct_evaluate(evaluate, leaves)
+            if i == 0 and noise is not None:
+                priors = self._puct_leaf_noise(noise, priors, leaves, 1)
             leaves = self.puct_advance(priors, vals, more=i < S - 1)
         visits = self.puct_result()
         actions = self.puct_pick(sample)
@@ -1048,7 +1164,8 @@ class VecOthelloEnv(object):
         _, rewards, dones, _ = self.step(actions, observe=False)
         if record:
             self.replay_label(rewards, dones)
-        _, kept = self.puct_reroot(actions, kept=True)
+        rp = None if noise is None else self._puct_root_noise(noise, evaluate)
+        _, kept = self.puct_reroot(actions, root_priors=rp, kept=True)
         return PuctPlay(actions, visits, rewards, dones, kept)
 
     # ------------------------------------------------------------ the replay store

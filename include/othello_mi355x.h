@@ -645,8 +645,8 @@ int oth_puct_result(oth_env *env, const oth_puct_params *p, void *workspace, uin
  *     children, each child's P becomes root_priors[e][square] clamped to [0,
  *     OTH_PUCT_PRIOR_MAX], before the selection of step 5.  Kept roots only: a
  *     fresh root gets its priors at its first advance.  This is how root noise
- *     is applied again: evaluate the observation of the stepped handle, mix the
- *     noise, quantise, pass the result here.
+ *     is applied again: evaluate the stepped handle's position, mix the noise
+ *     in (oth_puct_noise in root mode, below), pass the result here.
  *  5. Pending leaf.  Whatever leaf was pending before the call is discarded
  *     (its node stays as it is and can be selected again).  A DONE board whose
  *     root's v < OTH_PUCT_MAX_SIMS runs step 4 of oth_puct_advance from the
@@ -666,6 +666,68 @@ int oth_puct_pick(oth_env *env, const oth_puct_params *p, void *workspace, uint6
 int oth_puct_reroot(oth_env *env, const oth_puct_params *p, void *workspace, uint64_t workspace_bytes,
                     const int32_t *actions, const int32_t *root_priors, uint8_t *kept,
                     const oth_puct_leaves *leaves, oth_stream_t stream);
+
+/* Dirichlet root noise for self-play, in integers: oth_puct_noise mixes a keyed
+ * draw into the priors of the handle's position, so that a self-play run stays
+ * an exact function of the boards, the parameters, the weight bytes and the
+ * seeds.  It reads the handle and never writes it, and it knows nothing of a
+ * search's workspace: it maps rows of priors to rows of priors.
+ *
+ * Shapes.  K = rows_per_board in [1, OTH_PUCT_MAX_LEAVES]; priors_in and
+ * priors_out are int32[E K][N*N] and may be the same array (otherwise they must
+ * not overlap); kind uint8[E K] and boards uint64[E K][2W] are a search's leaf
+ * arrays (struct oth_puct_leaves), both given or both NULL; table uint32[4096]
+ * is a gamma table on the device (below).
+ *
+ * Which rows take noise.  The row of board e is row e K; every other row, and
+ * the row of a board that is not applied, is copied unchanged (where priors_in
+ * == priors_out nothing is written to those rows).  Board e is applied
+ *   - in root mode (kind and boards NULL; for oth_puct_reroot's root_priors):
+ *     always;
+ *   - in leaf mode (for the priors of an advance): where kind[e K] ==
+ *     OTH_PUCT_LEAF_EXPAND and the 2W words of boards[e K] equal the handle's
+ *     board e, that is, where the pending leaf is the root itself (a deeper
+ *     leaf has more discs, so nothing else needs comparing).  In a batch
+ *     search a root leaf can only sit in slot 0: the Select takes slot after
+ *     slot, a root without children is slot 0's leaf, and any later slot's
+ *     descent ends on that same root, which is a collision and closes the board
+ *     for the launch; at begin and at a re-root a fresh or unexpanded root is
+ *     slot 0's leaf alone.
+ *
+ * The draw.  Let the legal squares a be those of the handle's stored
+ * possible_moves, restricted to the board, in ascending order (noise only ever
+ * goes to the handle's position, so the call takes no legal array).  g_a =
+ * min(table[u_a >> 20], OTH_NOISE_G_MAX), u_a = word a & 3 of the
+ * Philox4x32-10 block of key `seed` and counter words (id, counter lo, counter
+ * hi, 6 | (a >> 2) << 8): purpose 6, a purpose of its own, with the block of
+ * four squares in bits 8 .. 15 of the purpose word, so that no counter
+ * arithmetic of a caller can collide with it; id = id_key + env_id_base + e mod
+ * 2^32.  Any 64-bit counter is accepted and is baked into the launch (a
+ * captured call replays the same draw); the draw depends on the global env id,
+ * the counter and the square alone: a sharded run equals the unsharded one.
+ *
+ * The mix.  G = the sum of the g_a (at most 2^32).  No legal square, or G = 0:
+ * the row is copied.  Otherwise eta_a = floor((65535 g_a + floor(G / 2)) / G)
+ * (oth_net_eval's rounding of a prior), and on the legal squares
+ *   out_a = ((256 - epsilon) clamp(in_a, 0, 65535) + epsilon eta_a + 128) >> 8,
+ * epsilon in [0, 256] in units of 1/256; the other squares of the row are
+ * copied.  (epsilon = 0 leaves the clamped inputs.)
+ *
+ * The table holds 4,096 quantiles of Gamma(alpha, 1), scaled so that the
+ * largest is 2^24 - 1: normalised gamma draws are a Dirichlet(alpha) draw, and
+ * the normalisation makes the scale free.  The library takes any table; the
+ * Python package makes one on the host (dirichlet_table).  A very small alpha
+ * gives mostly zero entries, and with them rows that take no noise (G = 0).
+ *
+ * OTH_EINVAL, with nothing launched: a NULL handle, priors or table; exactly
+ * one of kind and boards; rows_per_board outside [1, OTH_PUCT_MAX_LEAVES];
+ * epsilon outside [0, 256]; E K not fitting 31 bits.  The call only enqueues
+ * work and is capturable. */
+#define OTH_NOISE_TABLE 4096      /* entries of a gamma table */
+#define OTH_NOISE_G_MAX (1 << 24) /* entries are clamped to this */
+int oth_puct_noise(oth_env *env, int32_t rows_per_board, const uint8_t *kind, const uint64_t *boards,
+                   const int32_t *priors_in, int32_t *priors_out, int32_t epsilon, const uint32_t *table,
+                   uint64_t seed, uint32_t id_key, uint64_t counter, oth_stream_t stream);
 
 /* The batch calls: K leaves a board per launch under virtual loss, so that a
  * network sees E K rows a call and a move of S simulations needs about S / K
