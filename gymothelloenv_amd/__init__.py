@@ -9,7 +9,7 @@ terminal/score) as HIP kernels for gfx950 behind a C ABI
     SimpleOthelloEnv,        reference's constructor / attributes / 4-tuple step
     OthelloEnv
     RandomPolicy, GreedyPolicy, MaxiMinPolicy, MonteCarloPolicy, MCTSPolicy, PUCTPolicy,
-    SolverPolicy, SearchPolicy,
+    SolverPolicy, SearchPolicy, NetPolicy,
     make_state, undo_state
     default_search_weights   the conventional square weights of VecOthelloEnv.search
     SearchConfig             a search as a player: VecOthelloEnv.play_search, and the
@@ -25,6 +25,8 @@ terminal/score) as HIP kernels for gfx950 behind a C ABI
     symmetry_permutations            board symmetry, and the eight square permutations sigma_s
     DeviceNet, MLPPolicyValue,       the int8 policy-value network evaluated on the device (oth_net_eval): an
     net_features                     evaluator without a float, the float module a learner trains, its inputs
+    NetPlayer                        a DeviceNet as a player: VecOthelloEnv.play_net, and the opponent of
+                                     reset_vs / step_vs (argmax of the logits, or a draw from the priors)
     RootNoise, dirichlet_table       Dirichlet root noise for self-play, drawn on the device in integers
                                      (VecOthelloEnv.puct_noise; puct_search / puct_play take noise=RootNoise(...))
 """
@@ -40,7 +42,7 @@ def __getattr__(name):
                 "symmetry_masks", "symmetry_permutations"):
         from . import vec_env
         return getattr(vec_env, name)
-    if name in ("DeviceNet", "MLPPolicyValue", "net_features"):
+    if name in ("DeviceNet", "MLPPolicyValue", "net_features", "NetPlayer"):
         from . import net
         return getattr(net, name)
     if name in ("RootNoise", "dirichlet_table"):
@@ -50,7 +52,7 @@ def __getattr__(name):
         from . import othello
         return getattr(othello, name)
     if name in ("RandomPolicy", "GreedyPolicy", "MaxiMinPolicy", "MonteCarloPolicy", "MCTSPolicy",
-                "PUCTPolicy", "SolverPolicy", "SearchPolicy"):
+                "PUCTPolicy", "SolverPolicy", "SearchPolicy", "NetPolicy"):
         from . import policies
         return getattr(policies, name)
     if name in ("masked_sample", "masked_log_prob"):

@@ -55,6 +55,7 @@ OTH_REPLAY_MAX_HORIZON, OTH_REPLAY_MAX_ROWS, OTH_REPLAY_MAX_BATCH = 65536, 1 << 
 OTH_REPLAY_EMPTY, OTH_REPLAY_OPEN, OTH_REPLAY_LABELLED = range(3)
 OTH_NET_MAX_LAYERS, OTH_NET_MAX_WIDTH, OTH_NET_MAX_SHIFT = 4, 512, 24  # oth_net_*
 OTH_NET_BIAS_MAX, OTH_NET_MAX_ROWS = 1 << 30, 1 << 24
+OTH_NET_SAMPLE_DISCS_MAX = 257
 OTH_GRAPH_SLOTS = 64
 OTH_GRAPH_COUNTER_SHIFT = 40
 
@@ -147,6 +148,15 @@ class OthNetParams(ctypes.Structure):
                 ("value_shift", ctypes.c_int32)]
 
 
+class OthNetPolicy(ctypes.Structure):
+    """struct oth_net_policy (include/othello_mi355x.h): one colour's network as a
+    player, host memory read during the call; `blob` is a device address."""
+    _fields_ = [("params", OthNetParams),
+                ("blob", ctypes.c_void_p),
+                ("blob_bytes", ctypes.c_uint64),
+                ("sample_discs", ctypes.c_int32)]
+
+
 # every symbol include/othello_mi355x.h declares: (restype, argtypes)
 _P = ctypes.c_void_p
 _I32, _U32, _U64, _I64 = ctypes.c_int32, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_int64
@@ -188,6 +198,9 @@ SIGNATURES = {
     "oth_play_search": (_I32, [_P, _P, _P, _I32, _P, _P, _P, _P, _P]),
     "oth_reset_vs_search": (_I32, [_P, _P, _P, _P, _P]),
     "oth_step_vs_search": (_I32, [_P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "oth_play_net": (_I32, [_P, _P, _P, _I32, _P, _P, _P, _P]),
+    "oth_reset_vs_net": (_I32, [_P, _P, _P, _P, _P]),
+    "oth_step_vs_net": (_I32, [_P, _P, _P, _P, _P, _P, _P, _P]),
     "oth_reset_vs": (_I32, [_P, _I32, _P, _P, _P]),
     "oth_step_vs": (_I32, [_P, _I32, _P, _P, _P, _P, _P, _P]),
     "oth_step_vs_observe": (_I32, [_P, _I32, _P, _P, _P, _P, _P, _I32, _I32, _P, _P]),

@@ -894,6 +894,99 @@ int oth_step_vs_search(oth_env* env, const oth_search_policy* opponent, const in
     });
 }
 
+}  // extern "C"
+
+namespace {
+// an oth_net_policy's ranges that need no handle; who: the argument's name for the message
+int check_net_policy(const oth_net_policy* p, const char* who) {
+    char msg[200];
+    const char* why = nullptr;
+    NetParams np;
+    if (!p) why = "is NULL";
+    else if (!p->blob) why = "has a NULL blob";
+    else {
+        np.layers = p->params.layers;
+        np.width = p->params.width;
+        for (int l = 0; l < 4; ++l) np.shift[l] = p->params.shift[l];
+        np.policy_shift = p->params.policy_shift;
+        np.value_shift = p->params.value_shift;
+        why = net_check(8, &np);  // (the handle's board size is checked with blob_bytes, below)
+        if (!why && (reinterpret_cast<uintptr_t>(p->blob) & 15u)) why = "blob must be 16-byte aligned";
+        if (!why && (p->sample_discs < 0 || p->sample_discs > OTH_NET_SAMPLE_DISCS_MAX)) why = "sample_discs must be in [0, 257]";
+    }
+    if (!why) return OTH_OK;
+    snprintf(msg, sizeof(msg), "net policy `%s`: %s", who, why);
+    return fail(OTH_EINVAL, msg);
+}
+// ... and what needs the handle's board size
+int check_net_policy_size(const oth_env* env, const oth_net_policy* p, const char* who) {
+    char msg[200];
+    NetParams np;
+    np.layers = p->params.layers;
+    np.width = p->params.width;
+    for (int l = 0; l < 4; ++l) np.shift[l] = p->params.shift[l];
+    np.policy_shift = p->params.policy_shift;
+    np.value_shift = p->params.value_shift;
+    const char* why = net_check(env->n, &np);
+    if (!why && p->blob_bytes < net_geo(env->n, np).bytes()) why = "blob_bytes is below what oth_net_blob_bytes reports";
+    if (!why) return OTH_OK;
+    snprintf(msg, sizeof(msg), "net policy `%s`: %s", who, why);
+    return fail(OTH_EINVAL, msg);
+}
+}  // namespace
+
+extern "C" {
+
+int oth_play_net(oth_env* env, const oth_net_policy* black, const oth_net_policy* white, int32_t n_plies,
+                 int32_t* actions, int32_t* rewards, uint8_t* dones, oth_stream_t stream) {
+    // the argument checks come before the handle is read
+    if (!env) return fail(OTH_EINVAL, "NULL oth_env");
+    if (int rc = check_net_policy(black, "black")) return rc;
+    if (int rc = check_net_policy(white, "white")) return rc;
+    if (black->params.width != white->params.width)
+        return fail(OTH_EINVAL, "the two networks of oth_play_net must have the same width");
+    if (n_plies < 1) return fail(OTH_EINVAL, "n_plies must be >= 1");
+    if (int rc = check_net_policy_size(env, black, "black")) return rc;
+    if (int rc = check_net_policy_size(env, white, "white")) return rc;
+    if (int rc = use_device(env)) return rc;
+    const uint64_t ply0 = env->ply;
+    env->ply += (uint64_t)n_plies;
+    return with_n(env->n, [&](auto NC) {
+        return launch_play_net<decltype(NC)::value>(env, OTH_PLAY_SEARCH_PLAY, black, white, n_plies, nullptr, nullptr,
+                                                    nullptr, actions, rewards, dones, nullptr, ply0,
+                                                    (hipStream_t)stream);
+    });
+}
+
+int oth_reset_vs_net(oth_env* env, const oth_net_policy* opponent, const int8_t* protagonist, const uint8_t* mask,
+                     oth_stream_t stream) {
+    if (!env) return fail(OTH_EINVAL, "NULL oth_env");
+    if (int rc = check_net_policy(opponent, "opponent")) return rc;
+    if (int rc = check_net_policy_size(env, opponent, "opponent")) return rc;
+    if (int rc = use_device(env)) return rc;
+    const uint64_t call = env->ply++;
+    return with_n(env->n, [&](auto NC) {
+        return launch_play_net<decltype(NC)::value>(env, OTH_PLAY_SEARCH_RESET_VS, opponent, opponent, 0, nullptr,
+                                                    protagonist, mask, nullptr, nullptr, nullptr, nullptr, call,
+                                                    (hipStream_t)stream);
+    });
+}
+
+int oth_step_vs_net(oth_env* env, const oth_net_policy* opponent, const int32_t* actions, const int8_t* protagonist,
+                    int32_t* rewards, uint8_t* dones, int32_t* plies, oth_stream_t stream) {
+    if (!env) return fail(OTH_EINVAL, "NULL oth_env");
+    if (int rc = check_net_policy(opponent, "opponent")) return rc;
+    if (!actions) return fail(OTH_EINVAL, "actions is NULL");
+    if (int rc = check_net_policy_size(env, opponent, "opponent")) return rc;
+    if (int rc = use_device(env)) return rc;
+    const uint64_t call = env->ply++;
+    return with_n(env->n, [&](auto NC) {
+        return launch_play_net<decltype(NC)::value>(env, OTH_PLAY_SEARCH_STEP_VS, opponent, opponent, 0, actions,
+                                                    protagonist, nullptr, nullptr, rewards, dones, plies, call,
+                                                    (hipStream_t)stream);
+    });
+}
+
 int oth_reset_vs(oth_env* env, int32_t opponent_policy, const int8_t* protagonist, const uint8_t* mask,
                  oth_stream_t stream) {
     OTH_CHECK_ENV(env);

@@ -136,6 +136,14 @@ int launch_play_search(oth_env* env, int mode, const oth_search_policy* black, c
                        int32_t* rewards, uint8_t* dones, uint8_t* fb_ply, int32_t* plies, int32_t* fb_cnt,
                        uint64_t ctr, hipStream_t st);
 
+// k_play_net (oth_play_net, oth_reset_vs_net, oth_step_vs_net) in play_net_n.hip, every N, a unit of its own per
+// board size.  mode: which of the three (OTH_PLAY_SEARCH_*); the vs modes pass the opponent as both colours.  ctr:
+// the first ply's counter (play) or the call's (vs).  The arguments are checked; the two widths are equal.
+template <int N>
+int launch_play_net(oth_env* env, int mode, const oth_net_policy* black, const oth_net_policy* white, int n_plies,
+                    const int32_t* act_in, const int8_t* prot, const uint8_t* mask, int32_t* actions, int32_t* rewards,
+                    uint8_t* dones, int32_t* plies, uint64_t ctr, hipStream_t st);
+
 // k_mcts (oth_mcts) in mcts_n.hip, every N, a unit of its own per board size.  The arguments are checked.
 template <int N>
 int launch_mcts(oth_env* env, const oth_mcts_params* p, void* workspace, int32_t* visits, int32_t* wins2,

@@ -98,18 +98,9 @@ inline int play_search_move_host(const uint64_t* black, const uint64_t* white, c
 }  // namespace oth
 
 #if defined(__HIPCC__)
-#include "vs.hpp"
+#include "play_owner.hpp"
 
 namespace oth_dev {
-
-constexpr int PS_PLAY = 0, PS_STEP_VS = 1, PS_RESET_VS = 2;
-// a board's phase in the vs modes (vs.hpp's control flow cut where it may need a search), in the order it is gone through
-constexpr int VS_PRE = 0,     // the opponent replies before the protagonist's ply
-    VS_PROT = 1,              // the protagonist's ply
-    VS_POST = 2,              // the opponent replies after it
-    VS_END = 3,               // plies, tallies, auto-reset
-    VS_RESET_REPLY = 4,       // the opponent's replies of a reset (no openings, nothing reported)
-    VS_DONE = 5;
 
 // MODE PS_PLAY: side_b is black's policy, side_w white's, ctr the first ply's counter; the vs modes: both are
 // the opponent's, ctr the call's counter.  same: both sides read one weight table (one plane set is built).
@@ -140,155 +131,11 @@ __global__ __launch_bounds__(SOLVE_BLOCK) void k_play_search(
     if (!same) build_planes<N>(side_w.weights, g_planes[1]);  // (same: a kernel argument, uniform)
     const uint64_t* planes_w = same ? g_planes[0] : g_planes[1];
 
-    // ---- the owners' state
-    bool owner = lane < ne;
-    const int e = (int)(e0 + (owner ? lane : 0));
-    if (MODE == PS_RESET_VS && owner && mask && !mask[e]) owner = false;
-    const uint32_t id = rng.id_base + (uint32_t)e;
-    const uint64_t gbase = ctr * VS_PLIES_PER_CALL;
-    const Solo<N> eng(0, nullptr);
-    Lane<N> s;
-    s.black = zero<W>();
-    s.white = zero<W>();
-    s.legal = zero<W>();
-    s.meta = M_TERMINATED;
-    bool protw = true;
-    int p = 0;                                                   // play: the board's next ply
-    int ph = VS_DONE, r = 0, d = 1, win = NO_DISK, plies = 0, nfb = 0;  // vs: phase and the call's results
-    uint32_t j = 0;                                              // vs: the call's next draw
-    uint32_t cb = 0, cd = 0, cw = 0, vw = 0, vd = 0, vl = 0;
-    if (owner) {
-        if (MODE != PS_PLAY) protw = prot ? prot[e] == WHITE_DISK : true;
-        if (MODE == PS_RESET_VS) {
-            reset_lane<N>(s, rng.seed, id, ctr, RNG_OPENING_RESET, rng.init_rand);
-            ph = VS_RESET_REPLY;
-        } else {
-            load_lane<N>(s, boards, meta, legal, e);
-            if (MODE == PS_STEP_VS && !(s.meta & M_TERMINATED)) {
-                d = 0;
-                ph = VS_PRE;
-            }
-        }
-    }
-    auto has_move = [&]() { return any(s.legal & Geo<N>::BOARD); };
-    // play: ply p's outputs
-    auto record = [&](int a, int rr, int dd, int fb) {
-        const size_t o = (size_t)p * (size_t)E + (size_t)e;
-        if (actions) actions[o] = a;
-        if (rewards) rewards[o] = rr;
-        if (dones) dones[o] = (uint8_t)dd;
-        if (fb_ply) fb_ply[o] = (uint8_t)fb;
-    };
-    // play: ply p of a live board (k_play's ply)
-    auto play_ply = [&](int a, int fb) {
-        int rr, dd, ww;
-        step_lane<N>(s, a, flags, rr, dd, ww, eng);
-        if (dd) {
-            count_winner(ww, cb, cd, cw);
-            if (flags & OTH_AUTO_RESET) reset_lane<N>(s, rng.seed, id, ctr + (uint64_t)p, RNG_OPENING_AUTO, rng.init_rand);
-        }
-        record(a, rr, dd, fb);
-        ++p;
-    };
-    // vs: one ply; a reset's replies report nothing (reset_vs_lane)
-    auto vs_ply = [&](int a) {
-        if (ph == VS_RESET_REPLY) {
-            int rr, dd, ww;
-            step_lane<N>(s, a, flags, rr, dd, ww, eng);
-        } else {
-            step_lane<N>(s, a, flags, r, d, win, eng);
-        }
-    };
-    // the board through everything that needs no search; true: it wants a searched move now
-    auto advance = [&]() -> bool {
-        if constexpr (MODE == PS_PLAY) {
-            while (p < n_plies) {
-                if (s.meta & M_TERMINATED) {
-                    record(-1, 0, 1, 0);
-                    ++p;
-                    continue;
-                }
-                if ((s.meta >> M_RAND_SHIFT) > 0) {  // a random-opening ply
-                    const int a = random_action<N>(s, action_draw(rng.seed, id, ctr + (uint64_t)p));
-                    s.meta -= 1u << M_RAND_SHIFT;
-                    play_ply(a, 0);
-                    continue;
-                }
-                if (!has_move()) {  // GreedyPolicy's None: the invalid path
-                    play_ply(-1, 0);
-                    continue;
-                }
-                return true;
-            }
-            return false;
-        } else {
-            for (;;) {
-                if (ph == VS_DONE) return false;
-                if (ph == VS_PROT) {
-                    int a = act_in[e];
-                    const uint64_t g = gbase + j++;
-                    if ((s.meta >> M_RAND_SHIFT) > 0) {  // opening ply: the protagonist's action is replaced too
-                        a = random_action<N>(s, action_draw(rng.seed, id, g));
-                        s.meta -= 1u << M_RAND_SHIFT;
-                    }
-                    step_lane<N>(s, a, flags, r, d, win, eng);
-                    ph = d ? VS_END : VS_POST;
-                    continue;
-                }
-                if (ph == VS_END) {
-                    plies = (int)j;
-                    ph = VS_DONE;
-                    if (d) {
-                        count_winner(win, cb, cd, cw);
-                        const int pcol = protw ? WHITE_DISK : BLACK_DISK;
-                        vw += win == pcol;
-                        vd += win == NO_DISK;
-                        vl += win == -pcol;
-                        if (flags & OTH_AUTO_RESET) {
-                            reset_lane<N>(s, rng.seed, id, ctr, RNG_OPENING_AUTO, rng.init_rand);
-                            ph = VS_RESET_REPLY;
-                        }
-                    }
-                    continue;
-                }
-                // the reply phases: the opponent moves while it is to move and the game is on
-                const bool term = (s.meta & M_TERMINATED) != 0;
-                if (term || ((s.meta & M_TURN_WHITE) != 0) == protw) {
-                    if (ph == VS_PRE && !term) {
-                        ph = VS_PROT;
-                    } else if (ph == VS_RESET_REPLY) {
-                        ph = VS_DONE;
-                    } else {  // the game ended before the protagonist's ply, or the replies after it are over
-                        r = -r;
-                        ph = VS_END;
-                    }
-                    continue;
-                }
-                if (ph != VS_RESET_REPLY && (s.meta >> M_RAND_SHIFT) > 0) {
-                    const int a = random_action<N>(s, action_draw(rng.seed, id, gbase + j++));
-                    s.meta -= 1u << M_RAND_SHIFT;
-                    vs_ply(a);
-                    continue;
-                }
-                if (!has_move()) {
-                    ++j;
-                    vs_ply(-1);
-                    continue;
-                }
-                return true;
-            }
-        }
-    };
-    // the searched move (or the fallback's) of a board that wanted one
-    auto apply = [&](int a, int fb) {
-        if constexpr (MODE == PS_PLAY) {
-            play_ply(a, fb);
-        } else {
-            ++j;
-            nfb += fb;
-            vs_ply(a);
-        }
-    };
+    // ---- the owners' state and control flow (play_owner.hpp)
+    PlayOwner<N, MODE> o;
+    o.init(MODE, lane, e0, ne, boards, meta, legal, E, flags, n_plies, act_in, prot, mask, actions, rewards, dones,
+           fb_ply, rng, ctr);
+    const Lane<N>& s = o.s;
     if (lane < G) {
 #pragma unroll
         for (int k = 0; k < W; ++k) g_M[lane][k] = g_O[lane][k] = g_moves[lane][k] = 0ull;
@@ -300,7 +147,7 @@ __global__ __launch_bounds__(SOLVE_BLOCK) void k_play_search(
     for (;;) {
         bool want = false;
         if (lane < G) {
-            if (owner) want = advance();
+            if (o.owner) want = o.advance();
             int cnt = 0;
             if (want) {
                 const bool tw = (s.meta & M_TURN_WHITE) != 0;
@@ -350,42 +197,13 @@ __global__ __launch_bounds__(SOLVE_BLOCK) void k_play_search(
         __syncthreads();
         if (want) {
             const bool over = g_over[lane] != 0u;
-            apply(over ? 255 - (g_gkey[lane] & 255) : root_key_square(g_key[lane]), over ? 1 : 0);
+            o.apply(over ? 255 - (g_gkey[lane] & 255) : root_key_square(g_key[lane]), over ? 1 : 0);
         }
     }
 
-    // ---- the boards back, the call's outputs, the tallies
-    if (owner) {
-        store_lane<N>(s, boards, meta, legal, e);
-        if (MODE == PS_STEP_VS) {
-            if (rewards) rewards[e] = r;
-            if (dones) dones[e] = (uint8_t)d;
-            if (plies_out) plies_out[e] = plies;
-            if (fb_cnt) fb_cnt[e] = nfb;
-        }
-    }
-    if (MODE != PS_RESET_VS) {
-        // two blocks share a W/D/L slot (the handle has one per 16 boards): atomics without a return value
-        const size_t slot = 4 * (size_t)(blockIdx.x >> 1);
-        cb = wave_sum(cb);
-        cd = wave_sum(cd);
-        cw = wave_sum(cw);
-        if (lane == 0 && wdl) {
-            if (cb) atomicAdd(wdl + slot + 0, (unsigned long long)cb);
-            if (cd) atomicAdd(wdl + slot + 1, (unsigned long long)cd);
-            if (cw) atomicAdd(wdl + slot + 2, (unsigned long long)cw);
-        }
-        if (MODE == PS_STEP_VS) {
-            vw = wave_sum(vw);
-            vd = wave_sum(vd);
-            vl = wave_sum(vl);
-            if (lane == 0 && wdl_vs) {
-                if (vw) atomicAdd(wdl_vs + slot + 0, (unsigned long long)vw);
-                if (vd) atomicAdd(wdl_vs + slot + 1, (unsigned long long)vd);
-                if (vl) atomicAdd(wdl_vs + slot + 2, (unsigned long long)vl);
-            }
-        }
-    }
+    // ---- the boards back, the call's outputs, the tallies: two blocks share a W/D/L slot (the handle has one
+    // per 16 boards)
+    o.finish(boards, meta, legal, plies_out, fb_cnt, wdl, wdl_vs, (size_t)(blockIdx.x >> 1));
 }
 
 }  // namespace oth_dev

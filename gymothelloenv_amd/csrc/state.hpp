@@ -37,6 +37,7 @@ constexpr uint32_t RNG_ACTION = 0, RNG_OPENING_AUTO = 1, RNG_OPENING_RESET = 2;
 constexpr uint32_t RNG_PUCT_PICK = 4;  // oth_puct_pick's sampled move (3 is the sampler's, masked.hpp RNG_SAMPLE)
 constexpr uint32_t RNG_REPLAY_SAMPLE = 5;  // oth_replay_sample's row and symmetry (replay.hpp)
 constexpr uint32_t RNG_PUCT_NOISE = 6;  // oth_puct_noise's table draws (noise.hpp); bits 8 .. 15 hold the block of squares
+constexpr uint32_t RNG_NET_MOVE = 7;  // the network's sampled move (play_net.hpp: oth_play_net and the vs calls)
 
 template <int N>
 struct Start {  // _reset_board (othello.py:256-263): W at (c-1,c-1),(c,c); B at (c,c-1),(c-1,c)

@@ -6,6 +6,9 @@ oth_net_pack / oth_net_eval; include/othello_mi355x.h defines it in integers).
     net_features     the network's 3 N*N inputs as a float tensor, for training
     MLPPolicyValue   the float torch module on those features that a learner trains
     DeviceNet.from_module   the one as the other
+    NetPlayer        a DeviceNet as a player: VecOthelloEnv.play_net, and the embedded
+                     opponent of reset_vs / step_vs (oth_play_net, oth_reset_vs_net,
+                     oth_step_vs_net)
 
 A DeviceNet is an evaluator of VecOthelloEnv.puct_search / puct_play whose outputs
 go to the advance as they are (`quantized = True`): no float lies between the
@@ -223,3 +226,39 @@ class DeviceNet(object):
         of `>> shift`, which is exact where shift = 0."""
         weights, biases, shifts, ps, vs = cls.quantize_module(module)
         return cls(module.board_size, weights, biases, shifts, ps, vs, device=device)
+
+
+class NetPlayer(object):
+    """A network as a player (struct oth_net_policy): the move of a board is the
+    legal square of the largest logit of `net` (a DeviceNet), the lowest square of
+    equals, once the board holds at least `sample_discs` discs; with fewer discs it
+    is drawn in proportion to the network's priors (Philox purpose 7, keyed by the
+    env's seed, its global id and the ply's index: reproducible and shardable).
+    sample_discs = 0 (the default) never samples, 257 always does; on 8 x 8,
+    sample_discs = 12 samples the first eight discs placed.  Used by
+    VecOthelloEnv.play_net and as `opponent` of reset_vs / step_vs.  The struct is
+    built once and keeps the net's packed weights alive, so a captured call copies
+    nothing."""
+
+    def __init__(self, net, sample_discs=0):
+        if not isinstance(net, DeviceNet):
+            raise TypeError("NetPlayer takes a DeviceNet")
+        if isinstance(sample_discs, bool) or int(sample_discs) != sample_discs:
+            raise ValueError("sample_discs must be an integer")
+        if not 0 <= int(sample_discs) <= L.OTH_NET_SAMPLE_DISCS_MAX:
+            raise ValueError("sample_discs must be in [0, %d]" % L.OTH_NET_SAMPLE_DISCS_MAX)
+        self.net, self.sample_discs = net, int(sample_discs)
+        self._struct = L.OthNetPolicy(net.params, net.blob.data_ptr(), net.blob.numel(), self.sample_discs)
+
+    def _policy(self, env):
+        """The struct, for an env of the net's board size on the net's device."""
+        if env.board_size != self.net.board_size:
+            raise ValueError("the network is for %d x %d boards, the env has %d x %d" % (
+                self.net.board_size, self.net.board_size, env.board_size, env.board_size))
+        if torch.device(env.device) != self.net.device:
+            raise ValueError("the network lives on %s, the env on %s" % (self.net.device, env.device))
+        return self._struct
+
+    def __repr__(self):
+        return "NetPlayer(<%d x %d, %d layers of %d>, sample_discs=%d)" % (
+            self.net.board_size, self.net.board_size, self.net.layers, self.net.width, self.sample_discs)

@@ -306,4 +306,45 @@ class SearchPolicy(object):
         return self.get_action(obs)
 
 
-__all__ = ['RandomPolicy', 'GreedyPolicy', 'MaxiMinPolicy', 'MonteCarloPolicy', 'MCTSPolicy', 'PUCTPolicy', 'SolverPolicy', 'SearchPolicy', 'PROTAGONIST_TURN', 'OPPONENT_TURN', 'WHITE_DISK']
+class NetPolicy(object):
+    """A network as a player (no reference counterpart; the frozen-network opponent
+    of self-play learners): the move is VecOthelloEnv.play_net's for the board --
+    the legal square of the largest logit of `net` (a DeviceNet), the lowest square
+    of equals, and a draw from the priors while the board holds fewer than
+    `sample_discs` discs.  The move is computed by the same kernel: the board is
+    copied to a one-board scratch env, which plays one ply of NetPlayer(net,
+    sample_discs); seed(seed) keys the scratch env's draws."""
+
+    def __init__(self, net, sample_discs=0, seed=0):
+        from .net import NetPlayer
+        self.env = None
+        self.player = NetPlayer(net, sample_discs)
+        self._seed = int(seed)
+        self._scratch = None
+
+    def reset(self, env):
+        self.env = _base(env)
+
+    def seed(self, seed):
+        if seed is not None and int(seed) != self._seed:
+            self._seed = int(seed)
+            self._scratch = None
+
+    def get_action(self, obs):
+        from .vec_env import VecOthelloEnv
+        vec = self.env._vec
+        self.env._sync()
+        if self._scratch is None or self._scratch.board_size != vec.board_size:
+            self._scratch = VecOthelloEnv(1, board_size=vec.board_size, sudden_death_on_invalid_move=False,
+                                          seed=self._seed, device=vec.device)
+        self._scratch.set_state(*vec.get_state())
+        a = int(self._scratch.play_net(self.player, n_plies=1)[0].cpu()[0, 0])
+        if a < 0:
+            raise ValueError('no possible moves')
+        return a
+
+    def get_test_action(self, obs):
+        return self.get_action(obs)
+
+
+__all__ = ['RandomPolicy', 'GreedyPolicy', 'MaxiMinPolicy', 'MonteCarloPolicy', 'MCTSPolicy', 'PUCTPolicy', 'SolverPolicy', 'SearchPolicy', 'NetPolicy', 'PROTAGONIST_TURN', 'OPPONENT_TURN', 'WHITE_DISK']

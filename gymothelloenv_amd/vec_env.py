@@ -363,6 +363,33 @@ class VecOthelloEnv(object):
                                           _ptr(r), _ptr(d), _ptr(f), self._stream()), "oth_play_search")
         return (a, r, d, f) if fallbacks else (a, r, d)
 
+    def play_net(self, black, white=None, n_plies=1, record=True):
+        """n_plies plies where every board's mover plays its colour's network's move
+        (oth_play_net): step_policy with the policy's move replaced by the
+        NetPlayer's -- `black` for black's plies, `white` (None: `black`) for white's
+        -- in one launch that never synchronises the host: the argmax of the logits
+        over the stored legal squares, or a draw from the priors while the board has
+        fewer than the player's sample_discs discs.  The two networks must have the
+        same width.  Random-opening plies, terminated boards, auto-reset, the tallies
+        and the ply counter are step_policy's.
+
+        Returns (actions, rewards, dones) of shape (n_plies, E) (None if not
+        recorded)."""
+        from .net import NetPlayer
+        if not isinstance(black, NetPlayer) or not (white is None or isinstance(white, NetPlayer)):
+            raise TypeError("play_net takes NetPlayer objects")
+        n_plies = int(n_plies)
+        if n_plies < 1:
+            raise ValueError("n_plies must be >= 1")
+        pb = black._policy(self)
+        pw = pb if white is None or white is black else white._policy(self)
+        a = r = d = None
+        if record:
+            a, r, d = self._i32(n_plies, self.num_envs), self._i32(n_plies, self.num_envs), self._u8(n_plies, self.num_envs)
+        L.check(self._lib.oth_play_net(self._h, ctypes.addressof(pb), ctypes.addressof(pw), n_plies, _ptr(a), _ptr(r),
+                                       _ptr(d), self._stream()), "oth_play_net")
+        return a, r, d
+
     # ------------------------------------------- OthelloEnv semantics on device
     def _protagonist(self, protagonist):
         if protagonist is None:
@@ -380,9 +407,15 @@ class VecOthelloEnv(object):
         embedded opponent (`opponent` = 'random' | 'greedy', played on the device)
         replies until the protagonist (+1 white, the reference default, or -1
         black; int or per-board tensor) is to move.  `opponent` may be a
-        SearchConfig: the opponent then plays its searched move (oth_reset_vs_search)."""
+        SearchConfig: the opponent then plays its searched move (oth_reset_vs_search);
+        or a NetPlayer: it plays its network's move (oth_reset_vs_net)."""
+        from .net import NetPlayer
         prot = self._protagonist(protagonist)
         m = None if mask is None else mask.to(device=self.device, dtype=torch.uint8).contiguous()
+        if isinstance(opponent, NetPlayer):
+            L.check(self._lib.oth_reset_vs_net(self._h, ctypes.addressof(opponent._policy(self)), _ptr(prot), _ptr(m),
+                                               self._stream()), "oth_reset_vs_net")
+            return self.get_observation()
         if isinstance(opponent, SearchConfig):
             L.check(self._lib.oth_reset_vs_search(self._h, ctypes.addressof(opponent._policy(self)), _ptr(prot),
                                                   _ptr(m), self._stream()), "oth_reset_vs_search")
@@ -404,12 +437,28 @@ class VecOthelloEnv(object):
         (oth_step_vs_search, one launch, no host round trip per reply), the
         observation comes from an observe launch after it, and with fallbacks=True
         a fifth result counts, per board, the opponent's plies of this call whose
-        search ran over max_nodes and were played by GreedyPolicy (int32 (E,))."""
+        search ran over max_nodes and were played by GreedyPolicy (int32 (E,)).
+
+        `opponent` may be a NetPlayer: the opponent plays its network's move
+        (oth_step_vs_net, one launch, no host round trip per reply) and the
+        observation comes from an observe launch after it; fallbacks=True raises."""
+        from .net import NetPlayer
         prot = self._protagonist(protagonist)
         a = actions.to(device=self.device, dtype=torch.int32).contiguous()
         if a.numel() != self.num_envs:
             raise ValueError("expected %d actions, got %d" % (self.num_envs, a.numel()))
         r, d, n = self._i32(self.num_envs), self._u8(self.num_envs), self._i32(self.num_envs)
+        if isinstance(opponent, NetPlayer):
+            if fallbacks:
+                raise ValueError("fallbacks are a search opponent's: a NetPlayer has none")
+            o = None
+            if observe:
+                lay, o = self._obs_out(obs_layout, obs_dtype, obs)
+            L.check(self._lib.oth_step_vs_net(self._h, ctypes.addressof(opponent._policy(self)), _ptr(a), _ptr(prot),
+                                              _ptr(r), _ptr(d), _ptr(n), self._stream()), "oth_step_vs_net")
+            if observe:
+                L.check(self._lib.oth_observe(self._h, lay, _DTYPES[o.dtype], _ptr(o), self._stream()), "oth_observe")
+            return o, r, d.view(torch.bool), n
         if isinstance(opponent, SearchConfig):
             f = self._i32(self.num_envs) if fallbacks else None
             o = None

@@ -116,6 +116,9 @@ enum {
  *     ply g is word g % 4 of the block with counter g / 4.  Purpose 3: the
  *     sampler's uniform is (word 0 of the block with the sample counter) >> 8,
  *     times 2^-24.
+ *     Purposes 4 (oth_puct_pick), 5 (oth_replay_sample), 6 (oth_puct_noise)
+ *     and 7 (the network's sampled move: oth_play_net, oth_reset_vs_net,
+ *     oth_step_vs_net) are stated with those calls.
  *   - random-opening lengths: three murmur3 32-bit finalisers (fmix32),
  *       key = fmix32(seed lo ^ fmix32(seed hi ^ purpose * 0x7FEB352D)),
  *       word = fmix32(fmix32(key ^ ply lo ^ ply hi * 0x9E3779B9) ^ id),
@@ -1149,6 +1152,76 @@ int oth_reset_vs_search(oth_env *env, const oth_search_policy *opponent, const i
 int oth_step_vs_search(oth_env *env, const oth_search_policy *opponent, const int32_t *actions,
                        const int8_t *protagonist, int32_t *rewards, uint8_t *dones, int32_t *plies,
                        int32_t *fallbacks, oth_stream_t stream);
+
+/* The network as a player: one colour's (or the embedded opponent's) move
+ * chooser is an oth_net network.  The struct is host memory, read during the
+ * call; its values are baked into the launch, so the calls below stay capturable
+ * into a HIP graph.
+ *
+ * The network's move P(board, p).  M is the board's stored possible_moves on
+ * the board's squares (the root list S reads); z and prior[] are oth_net_eval's
+ * logits and priors of the row (the board's black words, white words, the turn
+ * bit of its meta, its stored legal words) with p.params and p.blob; D is the
+ * number of discs on the board, popcount(black | white).
+ *   D >= p.sample_discs: the move is the square of M with the largest z[a], the
+ *     lowest square among equals.  No prior takes part: logits that differ by
+ *     less than one step of a prior still decide.
+ *   D <  p.sample_discs: a draw in proportion to the priors, oth_puct_pick's
+ *     rule on prior[].  P = the sum of prior[a] over M (at least 1: the largest
+ *     logit's prior is at least 65535 / |M|); u = word 0 of the Philox4x32-10
+ *     block with key `seed` and counter words (id, g lo, g hi, 7) -- purpose 7,
+ *     a purpose of its own beside the seven of the draws above -- with id the
+ *     global env id (env_id_base + e mod 2^32) and g the ply's global index, the
+ *     one a random move of that ply would be drawn with: ply counter + p in
+ *     oth_play_net, c*256 + j in the vs calls; r = floor(u P / 2^32); the move
+ *     is the first square of M in ascending order whose cumulative prior exceeds
+ *     r.  A legal square of prior 0 is never drawn.
+ * sample_discs = 0 is a deterministic player, 257 always samples; on 8 x 8,
+ * sample_discs = 12 samples the first eight discs placed. */
+#define OTH_NET_SAMPLE_DISCS_MAX 257
+typedef struct oth_net_policy {
+    oth_net_params params;   /* as oth_net_eval takes them */
+    const void *blob;        /* DEVICE: oth_net_pack's bytes, 16-byte aligned */
+    uint64_t blob_bytes;     /* at least what oth_net_blob_bytes reports */
+    int32_t sample_discs;    /* [0, 257] */
+} oth_net_policy;
+
+/* oth_play_net: oth_step_policy with the policy's move replaced by P: black's
+ * plies use *black, white's *white (the two may be the same pointer; neither
+ * may be NULL).  Everything else is oth_step_policy's contract, as
+ * oth_play_search states it: a random move while random-opening plies remain,
+ * drawn for ply g = ply counter + p; an already terminated board gives action
+ * -1, done 1, reward 0; a live board with an empty stored mask plays action -1;
+ * OTH_AUTO_RESET resets a board after its terminal ply; the tallies are
+ * oth_counts'; the ply counter advances by n_plies; inside a graph region the
+ * slot's ply offset is added.  Outputs are [n_plies][E], each may be NULL.
+ * The two networks must have the same width (the kernel's accumulators are a
+ * compile-time width / 64): another width is OTH_EINVAL.  layers, the shifts and
+ * the weights may differ.
+ *
+ * oth_reset_vs_net / oth_step_vs_net are oth_reset_vs / oth_step_vs with the
+ * opponent's policy move replaced by P(board, *opponent), in a reset's replies
+ * too; the control flow, the draws (ply j of call c uses counter c*256 + j), the
+ * negated reward, plies, both tallies, the reset_vs-style OTH_AUTO_RESET and the
+ * one ply counter consumed per call are theirs, exactly as the _search calls
+ * state it.  For the observation, call oth_observe after it.
+ *
+ * One launch each (a wave per 16 boards: a tile of rows on the matrix cores); no
+ * call synchronises the host.  OTH_EINVAL, checked before the handle's device is
+ * touched and with nothing launched: a NULL handle, a NULL policy, a NULL blob, a
+ * field of params out of range for the handle's board size, blob_bytes below
+ * what oth_net_blob_bytes reports, a blob that is not 16-byte aligned,
+ * sample_discs outside [0, 257], two widths in oth_play_net, n_plies < 1, NULL
+ * actions in oth_step_vs_net.  The host cannot read a blob: one packed for
+ * another geometry or other shifts is found by the kernel, which then changes
+ * nothing -- no board, no output, no tally (oth_net_eval's rule); the ply
+ * counter has advanced all the same. */
+int oth_play_net(oth_env *env, const oth_net_policy *black, const oth_net_policy *white, int32_t n_plies,
+                 int32_t *actions, int32_t *rewards, uint8_t *dones, oth_stream_t stream);
+int oth_reset_vs_net(oth_env *env, const oth_net_policy *opponent, const int8_t *protagonist, const uint8_t *mask,
+                     oth_stream_t stream);
+int oth_step_vs_net(oth_env *env, const oth_net_policy *opponent, const int32_t *actions, const int8_t *protagonist,
+                    int32_t *rewards, uint8_t *dones, int32_t *plies, oth_stream_t stream);
 
 /* possible_moves of every env as masks uint64[E][W] (othello.py:242, :270, :466). */
 int oth_legal(oth_env *env, uint64_t *out, oth_stream_t stream);
