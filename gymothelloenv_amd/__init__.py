@@ -27,6 +27,8 @@ terminal/score) as HIP kernels for gfx950 behind a C ABI
     net_features                     evaluator without a float, the float module a learner trains, its inputs
     NetPlayer                        a DeviceNet as a player: VecOthelloEnv.play_net, and the opponent of
                                      reset_vs / step_vs (argmax of the logits, or a draw from the priors)
+    DeviceConvNet, ConvPolicyValue   the int8 residual convolutional network on the device (oth_cnet_eval) and
+                                     the float module a learner trains: an evaluator as a DeviceNet is
     RootNoise, dirichlet_table       Dirichlet root noise for self-play, drawn on the device in integers
                                      (VecOthelloEnv.puct_noise; puct_search / puct_play take noise=RootNoise(...))
 """
@@ -45,6 +47,9 @@ def __getattr__(name):
     if name in ("DeviceNet", "MLPPolicyValue", "net_features", "NetPlayer"):
         from . import net
         return getattr(net, name)
+    if name in ("DeviceConvNet", "ConvPolicyValue"):
+        from . import cnet
+        return getattr(cnet, name)
     if name in ("RootNoise", "dirichlet_table"):
         from . import noise
         return getattr(noise, name)

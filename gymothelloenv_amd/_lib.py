@@ -56,6 +56,7 @@ OTH_REPLAY_EMPTY, OTH_REPLAY_OPEN, OTH_REPLAY_LABELLED = range(3)
 OTH_NET_MAX_LAYERS, OTH_NET_MAX_WIDTH, OTH_NET_MAX_SHIFT = 4, 512, 24  # oth_net_*
 OTH_NET_BIAS_MAX, OTH_NET_MAX_ROWS = 1 << 30, 1 << 24
 OTH_NET_SAMPLE_DISCS_MAX = 257
+OTH_CNET_MAX_BLOCKS = 8  # oth_cnet_*
 OTH_GRAPH_SLOTS = 64
 OTH_GRAPH_COUNTER_SHIFT = 40
 
@@ -148,6 +149,17 @@ class OthNetParams(ctypes.Structure):
                 ("value_shift", ctypes.c_int32)]
 
 
+class OthCnetParams(ctypes.Structure):
+    """struct oth_cnet_params (include/othello_mi355x.h): host memory read during the call."""
+    _fields_ = [("channels", ctypes.c_int32),
+                ("blocks", ctypes.c_int32),
+                ("shift_stem", ctypes.c_int32),
+                ("shift", ctypes.c_int32 * 16),
+                ("shift_head", ctypes.c_int32),
+                ("policy_shift", ctypes.c_int32),
+                ("value_shift", ctypes.c_int32)]
+
+
 class OthNetPolicy(ctypes.Structure):
     """struct oth_net_policy (include/othello_mi355x.h): one colour's network as a
     player, host memory read during the call; `blob` is a device address."""
@@ -195,6 +207,9 @@ SIGNATURES = {
     "oth_net_blob_bytes": (_I32, [_I32, _P, _P]),
     "oth_net_pack": (_I32, [_I32, _P, _P, _P, _P, _U64]),
     "oth_net_eval": (_I32, [_I32, _I32, _P, _P, _U64, _P, _P, _P, _P, _P, _P, _P]),
+    "oth_cnet_blob_bytes": (_I32, [_I32, _P, _P]),
+    "oth_cnet_pack": (_I32, [_I32, _P, _P, _P, _P, _U64]),
+    "oth_cnet_eval": (_I32, [_I32, _I32, _P, _P, _U64, _P, _P, _P, _P, _P, _P, _P]),
     "oth_play_search": (_I32, [_P, _P, _P, _I32, _P, _P, _P, _P, _P]),
     "oth_reset_vs_search": (_I32, [_P, _P, _P, _P, _P]),
     "oth_step_vs_search": (_I32, [_P, _P, _P, _P, _P, _P, _P, _P, _P]),

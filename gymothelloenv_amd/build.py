@@ -10,8 +10,9 @@ csrc/play_net_n.hip (oth_play_net, oth_reset_vs_net, oth_step_vs_net: the networ
 csrc/mcts_n.hip (oth_mcts) and csrc/puct_n.hip (oth_puct_begin, oth_puct_advance, oth_puct_result, oth_puct_pick,
 oth_puct_reroot) and csrc/replay_n.hip (oth_replay_begin, oth_replay_append, oth_replay_label, oth_replay_counts,
 oth_replay_gather, oth_replay_sample, oth_symmetry_masks) once per N,
-csrc/net.hip (oth_net_eval: the int8 network on the matrix cores) and csrc/noise.hip (oth_puct_noise: Dirichlet
-root noise in integers) once for every N,
+csrc/net.hip (oth_net_eval: the int8 network on the matrix cores), csrc/cnet.hip (oth_cnet_eval: the int8
+residual convolutional network on the matrix cores) and csrc/noise.hip (oth_puct_noise: Dirichlet root noise in
+integers) once for every N,
 csrc/capi.hip holds the C ABI, and the objects are linked into one shared library.
 
 Reproducibility: objects go to a fixed directory (`_objs/`, git-ignored) so the
@@ -37,7 +38,8 @@ SOURCES = ("capi.hip", "kernels_n.hip", "play_rand_n.hip", "masked.hip", "device
            "tables.hpp", "state.hpp", "engines.hpp", "policy.hpp", "play.hpp", "vs.hpp", "observe.hpp", "solve_n.hip",
            "solve.hpp", "root_tasks.hpp", "search_n.hip", "search.hpp", "play_search_n.hip", "play_search.hpp",
            "mcts_n.hip", "mcts.hpp", "puct_n.hip", "puct.hpp", "replay_n.hip", "replay.hpp", "net.hip", "net.hpp",
-           "noise.hip", "noise.hpp", "net_dev.hpp", "play_owner.hpp", "play_net_n.hip", "play_net.hpp")
+           "noise.hip", "noise.hpp", "net_dev.hpp", "play_owner.hpp", "play_net_n.hip", "play_net.hpp", "cnet.hip",
+           "cnet.hpp", "cnet_dev.hpp")
 PLAY_SIZES = list(range(4, 12))  # k_play_rand (one-word boards) and k_play_rand_w (two-word boards)
 # play_rand_n.hip: the max-ILP machine scheduler (one wave per SIMD: latency hidden by the schedule
 # counts, occupancy does not); the rest of the library keeps the default scheduler
@@ -113,6 +115,7 @@ def build(force=False, verbose=True, extra_flags=(), out=OUT, jobs=None, only_si
     units = [(os.path.join(CSRC, "capi.hip"), os.path.join(objdir, "capi.o"), ['-DOTH_SRC_HASH="%s"' % digest]),
              (os.path.join(CSRC, "masked.hip"), os.path.join(objdir, "masked.o"), []),
              (os.path.join(CSRC, "net.hip"), os.path.join(objdir, "net.o"), []),
+             (os.path.join(CSRC, "cnet.hip"), os.path.join(objdir, "cnet.o"), []),
              (os.path.join(CSRC, "noise.hip"), os.path.join(objdir, "noise.o"), [])]
     units += [(os.path.join(CSRC, "kernels_n.hip"), os.path.join(objdir, "kernels_n%d.o" % n), ["-DOTH_N=%d" % n])
               for n in SIZES]
@@ -150,7 +153,7 @@ def build(force=False, verbose=True, extra_flags=(), out=OUT, jobs=None, only_si
         keep = {os.path.basename(u[1]) for u in units
                 if os.path.basename(u[1]) == "capi.o" or os.path.basename(u[1]).startswith(tuple(only_units))}
     if only_sizes is not None:
-        keep = {"capi.o", "masked.o", "net.o", "noise.o"} | {"kernels_n%d.o" % n for n in only_sizes} | {"play_rand_n%d.o" % n
+        keep = {"capi.o", "masked.o", "net.o", "cnet.o", "noise.o"} | {"kernels_n%d.o" % n for n in only_sizes} | {"play_rand_n%d.o" % n
                                                                                    for n in only_sizes} | {
             "playouts_n%d.o" % n for n in only_sizes} | {"solve_n%d.o" % n for n in only_sizes} | {
             "search_n%d.o" % n for n in only_sizes} | {"play_search_n%d.o" % n for n in only_sizes} | {"play_net_n%d.o" % n for n in only_sizes} | {

@@ -12,6 +12,7 @@
 
 #include "launch.hpp"
 #include "net.hpp"
+#include "cnet.hpp"
 
 using namespace oth;
 using namespace oth_host;
@@ -786,6 +787,59 @@ int oth_net_eval(int32_t board_size, int32_t n_rows, const oth_net_params* param
     if (n_rows == 0) return OTH_OK;
     return launch_net_eval(board_size, params, n_rows, blob, boards, meta, legal, priors, values, logits,
                            (hipStream_t)stream);
+}
+
+namespace {
+// oth_cnet_params as cnet.hpp's CnetParams, checked: what every oth_cnet call does first
+int cnet_params(int32_t board_size, const oth_cnet_params* params, CnetParams* out) {
+    if (!params) return fail(OTH_EINVAL, "params is NULL");
+    out->channels = params->channels;
+    out->blocks = params->blocks;
+    out->shift_stem = params->shift_stem;
+    for (int l = 0; l < 16; ++l) out->shift[l] = params->shift[l];
+    out->shift_head = params->shift_head;
+    out->policy_shift = params->policy_shift;
+    out->value_shift = params->value_shift;
+    if (const char* why = cnet_check(board_size, out)) return fail(OTH_EINVAL, why);
+    return OTH_OK;
+}
+}  // namespace
+
+int oth_cnet_blob_bytes(int32_t board_size, const oth_cnet_params* params, uint64_t* bytes) {
+    if (!bytes) return fail(OTH_EINVAL, "bytes is NULL");
+    CnetParams cp;
+    if (int rc = cnet_params(board_size, params, &cp)) return rc;
+    *bytes = cnet_geo(board_size, cp).bytes();
+    return OTH_OK;
+}
+
+int oth_cnet_pack(int32_t board_size, const oth_cnet_params* params, const int8_t* w, const int32_t* b, void* blob,
+                  uint64_t blob_bytes) {
+    if (!w || !b || !blob) return fail(OTH_EINVAL, "w, b or blob is NULL");
+    CnetParams cp;
+    if (int rc = cnet_params(board_size, params, &cp)) return rc;
+    if (reinterpret_cast<uintptr_t>(blob) & 15u) return fail(OTH_EINVAL, "blob must be 16-byte aligned");
+    if (blob_bytes < cnet_geo(board_size, cp).bytes())
+        return fail(OTH_EINVAL, "blob_bytes is below what oth_cnet_blob_bytes reports");
+    if (const char* why = cnet_pack(board_size, cp, w, b, reinterpret_cast<uint8_t*>(blob))) return fail(OTH_EINVAL, why);
+    return OTH_OK;
+}
+
+int oth_cnet_eval(int32_t board_size, int32_t n_rows, const oth_cnet_params* params, const void* blob,
+                  uint64_t blob_bytes, const uint64_t* boards, const uint16_t* meta, const uint64_t* legal,
+                  int32_t* priors, int32_t* values, int32_t* logits, oth_stream_t stream) {
+    if (!blob) return fail(OTH_EINVAL, "blob is NULL");
+    if (!boards || !meta || !legal) return fail(OTH_EINVAL, "boards, meta or legal is NULL");
+    if (!priors || !values) return fail(OTH_EINVAL, "priors or values is NULL");
+    CnetParams cp;
+    if (int rc = cnet_params(board_size, params, &cp)) return rc;
+    if (n_rows < 0 || n_rows > OTH_NET_MAX_ROWS) return fail(OTH_EINVAL, "n_rows must be in [0, 2^24]");
+    if (reinterpret_cast<uintptr_t>(blob) & 15u) return fail(OTH_EINVAL, "blob must be 16-byte aligned");
+    if (blob_bytes < cnet_geo(board_size, cp).bytes())
+        return fail(OTH_EINVAL, "blob_bytes is below what oth_cnet_blob_bytes reports");
+    if (n_rows == 0) return OTH_OK;
+    return launch_cnet_eval(board_size, params, n_rows, blob, boards, meta, legal, priors, values, logits,
+                            (hipStream_t)stream);
 }
 
 int oth_puct_noise(oth_env* env, int32_t rows_per_board, const uint8_t* kind, const uint64_t* boards,

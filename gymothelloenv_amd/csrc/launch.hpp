@@ -228,6 +228,12 @@ int launch_net_eval(int n, const oth_net_params* p, int n_rows, const void* blob
                     const uint16_t* meta, const uint64_t* legal, int32_t* priors, int32_t* values, int32_t* logits,
                     hipStream_t st);
 
+// k_cnet_eval (oth_cnet_eval: the int8 residual convolutional network on n_rows >= 1 rows in exchange format) in
+// cnet.hip, one unit for every board size.  The arguments are checked.
+int launch_cnet_eval(int n, const oth_cnet_params* p, int n_rows, const void* blob, const uint64_t* boards,
+                     const uint16_t* meta, const uint64_t* legal, int32_t* priors, int32_t* values, int32_t* logits,
+                     hipStream_t st);
+
 // k_puct_noise (oth_puct_noise: Dirichlet root noise mixed into rows of priors) in noise.hip, one unit for every
 // board size.  The arguments are checked.
 int launch_puct_noise(oth_env* env, int rows_per_board, const uint8_t* kind, const uint64_t* boards,

@@ -1070,6 +1070,73 @@ int oth_net_eval(int32_t board_size, int32_t n_rows, const oth_net_params *param
                  uint64_t blob_bytes, const uint64_t *boards, const uint16_t *meta, const uint64_t *legal,
                  int32_t *priors, int32_t *values, int32_t *logits, oth_stream_t stream);
 
+/* The convolutional network: an int8 residual 3 x 3 convolutional policy-value
+ * network on the same rows, with the same outputs and under the same contract as
+ * oth_net_* above: every output is an exact integer function of the row, the
+ * parameters and the weight bytes; the calls are stateless and take no handle.
+ *
+ * Geometry.  N is the board size, nn = N N, square a = row N + col.  C =
+ * channels is 64 or 128, B = blocks in [1, OTH_CNET_MAX_BLOCKS].  Parameters
+ * (struct oth_cnet_params, host memory read during the call): channels, blocks,
+ * shift_stem, shift[l] for l < 2 B (the others are not read), shift_head,
+ * policy_shift, value_shift; every shift read is in [0, OTH_NET_MAX_SHIFT].
+ *
+ * conv(w, b, in)[o][y][x] = b[o] + sum_i sum_{dy, dx in {-1, 0, 1}}
+ *   w[o][i][dy + 1][dx + 1] in[i][y + dy][x + dx], with in = 0 off the board.
+ * clip(v) = min(127, max(0, v)); >> is the arithmetic shift.
+ *
+ * The input is three planes of 0 or 1 over the squares: the mover's discs (the
+ * white words where meta bit 0 is set, else the black words), the opponent's,
+ * and the legal squares.  Bits at or above nn and every other meta bit are
+ * never read.
+ *   stem:     h = clip(conv(3 -> C) >> shift_stem)
+ *   block k:  t = clip(conv_2k(h) >> shift[2k]),
+ *             h = clip((conv_2k+1(t) >> shift[2k+1]) + h)       k = 0 .. B - 1
+ *   head:     one conv C -> 16 with accumulators u[j][a]; the logit of square a is
+ *             z[a] = u[0][a], the raw accumulator; f[j][a] = clip(u[j][a] >>
+ *             shift_head) for j = 1 .. 15; z[nn] = bv + sum_a sum_{j = 1 .. 15}
+ *             wv[a][j - 1] f[j][a]; value = clamp(z[nn] >> value_shift, -32768,
+ *             32768).
+ * Priors: oth_net's integer softmax (above) over the legal squares from z[a],
+ * with EXP2 and policy_shift as there; a row without a legal square gets
+ * all-zero priors.
+ *
+ * No accumulator leaves int32: every bias satisfies |b| <= 2^30 =
+ * OTH_NET_BIAS_MAX; a conv's sum is at most 9 * 128 * 127 * 128 < 2^25 in
+ * magnitude beside it, the value's sum at most 15 * 256 * 127 * 128 < 2^26.
+ *
+ * Logical weights (oth_cnet_pack's host inputs), one after the other.  w: int8,
+ * the stem [C][3][3][3] as (o, i, ky, kx), the 2 B convs [C][C][3][3], the head
+ * [16][C][3][3], then wv [nn][15].  b: int32, the stem's C, the convs' 2 B C,
+ * the head's 16, then bv.
+ *
+ * oth_cnet_blob_bytes, oth_cnet_pack and oth_cnet_eval take what their oth_net_*
+ * namesakes take and fail as they do (OTH_EINVAL with nothing launched or
+ * written: NULL pointers (all but logits), a board size, a field of params or a
+ * bias out of range, blob_bytes below what oth_cnet_blob_bytes reports, a blob
+ * that is not 16-byte aligned, n_rows outside [0, OTH_NET_MAX_ROWS]).  The blob
+ * is opaque, holds no addresses and begins with two tags (geometry, shifts)
+ * whose prefixes differ from oth_net's; an evaluation that names another
+ * geometry or other shifts than the blob was packed for writes nothing.
+ * oth_cnet_eval is one launch (none for n_rows = 0), never synchronises and is
+ * capturable; logits int32[R][nn + 1] (z) may be NULL. */
+#define OTH_CNET_MAX_BLOCKS 8
+typedef struct oth_cnet_params {
+    int32_t channels;     /* C: 64 or 128 */
+    int32_t blocks;       /* B in [1, 8] */
+    int32_t shift_stem;   /* in [0, 24] */
+    int32_t shift[16];    /* shift[l], l < 2 B, in [0, 24] */
+    int32_t shift_head;   /* in [0, 24] */
+    int32_t policy_shift; /* in [0, 24] */
+    int32_t value_shift;  /* in [0, 24] */
+} oth_cnet_params;
+int oth_cnet_blob_bytes(int32_t board_size, const oth_cnet_params *params, uint64_t *bytes);
+int oth_cnet_pack(int32_t board_size, const oth_cnet_params *params, const int8_t *w, const int32_t *b, void *blob,
+                  uint64_t blob_bytes);
+int oth_cnet_eval(int32_t board_size, int32_t n_rows, const oth_cnet_params *params, const void *blob,
+                  uint64_t blob_bytes, const uint64_t *boards, const uint16_t *meta, const uint64_t *legal,
+                  int32_t *priors, int32_t *values, int32_t *logits, oth_stream_t stream);
+
 /* OthelloEnv (othello.py:96-214) for every env: the protagonist's colour per
  * env (protagonist: device int8[E] of +1 white / -1 black, NULL = all white,
  * the reference default) and an embedded opponent played on the device
