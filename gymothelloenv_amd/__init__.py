@@ -25,10 +25,11 @@ terminal/score) as HIP kernels for gfx950 behind a C ABI
     symmetry_permutations            board symmetry, and the eight square permutations sigma_s
     DeviceNet, MLPPolicyValue,       the int8 policy-value network evaluated on the device (oth_net_eval): an
     net_features                     evaluator without a float, the float module a learner trains, its inputs
-    NetPlayer                        a DeviceNet as a player: VecOthelloEnv.play_net, and the opponent of
-                                     reset_vs / step_vs (argmax of the logits, or a draw from the priors)
+    NetPlayer                        a DeviceNet or a DeviceConvNet as a player: VecOthelloEnv.play_net, and the
+                                     opponent of reset_vs / step_vs (argmax of the logits, or a draw from the
+                                     priors; oth_play_net for the MLP, oth_play_cnet for the conv net)
     DeviceConvNet, ConvPolicyValue   the int8 residual convolutional network on the device (oth_cnet_eval) and
-                                     the float module a learner trains: an evaluator as a DeviceNet is
+                                     the float module a learner trains: an evaluator and a player as a DeviceNet is
     RootNoise, dirichlet_table       Dirichlet root noise for self-play, drawn on the device in integers
                                      (VecOthelloEnv.puct_noise; puct_search / puct_play take noise=RootNoise(...))
 """

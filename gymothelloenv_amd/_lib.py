@@ -169,6 +169,15 @@ class OthNetPolicy(ctypes.Structure):
                 ("sample_discs", ctypes.c_int32)]
 
 
+class OthCnetPolicy(ctypes.Structure):
+    """struct oth_cnet_policy (include/othello_mi355x.h): one colour's convolutional
+    network as a player, host memory read during the call; `blob` is a device address."""
+    _fields_ = [("params", OthCnetParams),
+                ("blob", ctypes.c_void_p),
+                ("blob_bytes", ctypes.c_uint64),
+                ("sample_discs", ctypes.c_int32)]
+
+
 # every symbol include/othello_mi355x.h declares: (restype, argtypes)
 _P = ctypes.c_void_p
 _I32, _U32, _U64, _I64 = ctypes.c_int32, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_int64
@@ -216,6 +225,9 @@ SIGNATURES = {
     "oth_play_net": (_I32, [_P, _P, _P, _I32, _P, _P, _P, _P]),
     "oth_reset_vs_net": (_I32, [_P, _P, _P, _P, _P]),
     "oth_step_vs_net": (_I32, [_P, _P, _P, _P, _P, _P, _P, _P]),
+    "oth_play_cnet": (_I32, [_P, _P, _P, _I32, _P, _P, _P, _P]),
+    "oth_reset_vs_cnet": (_I32, [_P, _P, _P, _P, _P]),
+    "oth_step_vs_cnet": (_I32, [_P, _P, _P, _P, _P, _P, _P, _P]),
     "oth_reset_vs": (_I32, [_P, _I32, _P, _P, _P]),
     "oth_step_vs": (_I32, [_P, _I32, _P, _P, _P, _P, _P, _P]),
     "oth_step_vs_observe": (_I32, [_P, _I32, _P, _P, _P, _P, _P, _I32, _I32, _P, _P]),

@@ -6,7 +6,8 @@ compiled once per N (-DOTH_N=4..16) in parallel, csrc/play_rand_n.hip (the
 fused random-play kernels, its own scheduler flags) once per N = 4..11, csrc/playouts_n.hip
 (oth_playouts), csrc/solve_n.hip (oth_solve), csrc/search_n.hip (oth_search),
 csrc/play_search_n.hip (oth_play_search, oth_reset_vs_search, oth_step_vs_search),
-csrc/play_net_n.hip (oth_play_net, oth_reset_vs_net, oth_step_vs_net: the network as a player) and
+csrc/play_net_n.hip (oth_play_net, oth_reset_vs_net, oth_step_vs_net: the network as a player),
+csrc/play_cnet_n.hip (oth_play_cnet, oth_reset_vs_cnet, oth_step_vs_cnet: the conv net as a player) and
 csrc/mcts_n.hip (oth_mcts) and csrc/puct_n.hip (oth_puct_begin, oth_puct_advance, oth_puct_result, oth_puct_pick,
 oth_puct_reroot) and csrc/replay_n.hip (oth_replay_begin, oth_replay_append, oth_replay_label, oth_replay_counts,
 oth_replay_gather, oth_replay_sample, oth_symmetry_masks) once per N,
@@ -39,7 +40,7 @@ SOURCES = ("capi.hip", "kernels_n.hip", "play_rand_n.hip", "masked.hip", "device
            "solve.hpp", "root_tasks.hpp", "search_n.hip", "search.hpp", "play_search_n.hip", "play_search.hpp",
            "mcts_n.hip", "mcts.hpp", "puct_n.hip", "puct.hpp", "replay_n.hip", "replay.hpp", "net.hip", "net.hpp",
            "noise.hip", "noise.hpp", "net_dev.hpp", "play_owner.hpp", "play_net_n.hip", "play_net.hpp", "cnet.hip",
-           "cnet.hpp", "cnet_dev.hpp")
+           "cnet.hpp", "cnet_dev.hpp", "play_cnet_n.hip", "play_cnet.hpp")
 PLAY_SIZES = list(range(4, 12))  # k_play_rand (one-word boards) and k_play_rand_w (two-word boards)
 # play_rand_n.hip: the max-ILP machine scheduler (one wave per SIMD: latency hidden by the schedule
 # counts, occupancy does not); the rest of the library keeps the default scheduler
@@ -131,6 +132,8 @@ def build(force=False, verbose=True, extra_flags=(), out=OUT, jobs=None, only_si
                ["-DOTH_N=%d" % n]) for n in SIZES]
     units += [(os.path.join(CSRC, "play_net_n.hip"), os.path.join(objdir, "play_net_n%d.o" % n), ["-DOTH_N=%d" % n])
               for n in SIZES]
+    units += [(os.path.join(CSRC, "play_cnet_n.hip"), os.path.join(objdir, "play_cnet_n%d.o" % n), ["-DOTH_N=%d" % n])
+              for n in SIZES]
     units += [(os.path.join(CSRC, "mcts_n.hip"), os.path.join(objdir, "mcts_n%d.o" % n), ["-DOTH_N=%d" % n])
               for n in SIZES]
     units += [(os.path.join(CSRC, "puct_n.hip"), os.path.join(objdir, "puct_n%d.o" % n), ["-DOTH_N=%d" % n])
@@ -156,7 +159,7 @@ def build(force=False, verbose=True, extra_flags=(), out=OUT, jobs=None, only_si
         keep = {"capi.o", "masked.o", "net.o", "cnet.o", "noise.o"} | {"kernels_n%d.o" % n for n in only_sizes} | {"play_rand_n%d.o" % n
                                                                                    for n in only_sizes} | {
             "playouts_n%d.o" % n for n in only_sizes} | {"solve_n%d.o" % n for n in only_sizes} | {
-            "search_n%d.o" % n for n in only_sizes} | {"play_search_n%d.o" % n for n in only_sizes} | {"play_net_n%d.o" % n for n in only_sizes} | {
+            "search_n%d.o" % n for n in only_sizes} | {"play_search_n%d.o" % n for n in only_sizes} | {"play_net_n%d.o" % n for n in only_sizes} | {"play_cnet_n%d.o" % n for n in only_sizes} | {
             "mcts_n%d.o" % n for n in only_sizes} | {"puct_n%d.o" % n for n in only_sizes} | {
             "replay_n%d.o" % n for n in only_sizes}
     if only_sizes is not None or only_units is not None:

@@ -1041,6 +1041,100 @@ int oth_step_vs_net(oth_env* env, const oth_net_policy* opponent, const int32_t*
     });
 }
 
+}  // extern "C"
+
+namespace {
+CnetParams cnet_params_of(const oth_cnet_params& q) {
+    CnetParams cp;
+    cp.channels = q.channels;
+    cp.blocks = q.blocks;
+    cp.shift_stem = q.shift_stem;
+    for (int l = 0; l < 16; ++l) cp.shift[l] = q.shift[l];
+    cp.shift_head = q.shift_head;
+    cp.policy_shift = q.policy_shift;
+    cp.value_shift = q.value_shift;
+    return cp;
+}
+// an oth_cnet_policy's ranges that need no handle; who: the argument's name for the message
+int check_cnet_policy(const oth_cnet_policy* p, const char* who) {
+    char msg[200];
+    const char* why = nullptr;
+    if (!p) why = "is NULL";
+    else if (!p->blob) why = "has a NULL blob";
+    else {
+        const CnetParams cp = cnet_params_of(p->params);
+        why = cnet_check(8, &cp);  // (the handle's board size is checked with blob_bytes, below)
+        if (!why && (reinterpret_cast<uintptr_t>(p->blob) & 15u)) why = "blob must be 16-byte aligned";
+        if (!why && (p->sample_discs < 0 || p->sample_discs > OTH_NET_SAMPLE_DISCS_MAX)) why = "sample_discs must be in [0, 257]";
+    }
+    if (!why) return OTH_OK;
+    snprintf(msg, sizeof(msg), "cnet policy `%s`: %s", who, why);
+    return fail(OTH_EINVAL, msg);
+}
+// ... and what needs the handle's board size
+int check_cnet_policy_size(const oth_env* env, const oth_cnet_policy* p, const char* who) {
+    char msg[200];
+    const CnetParams cp = cnet_params_of(p->params);
+    const char* why = cnet_check(env->n, &cp);
+    if (!why && p->blob_bytes < cnet_geo(env->n, cp).bytes()) why = "blob_bytes is below what oth_cnet_blob_bytes reports";
+    if (!why) return OTH_OK;
+    snprintf(msg, sizeof(msg), "cnet policy `%s`: %s", who, why);
+    return fail(OTH_EINVAL, msg);
+}
+}  // namespace
+
+extern "C" {
+
+int oth_play_cnet(oth_env* env, const oth_cnet_policy* black, const oth_cnet_policy* white, int32_t n_plies,
+                  int32_t* actions, int32_t* rewards, uint8_t* dones, oth_stream_t stream) {
+    // the argument checks come before the handle is read
+    if (!env) return fail(OTH_EINVAL, "NULL oth_env");
+    if (int rc = check_cnet_policy(black, "black")) return rc;
+    if (int rc = check_cnet_policy(white, "white")) return rc;
+    if (black->params.channels != white->params.channels)
+        return fail(OTH_EINVAL, "the two networks of oth_play_cnet must have the same channels");
+    if (n_plies < 1) return fail(OTH_EINVAL, "n_plies must be >= 1");
+    if (int rc = check_cnet_policy_size(env, black, "black")) return rc;
+    if (int rc = check_cnet_policy_size(env, white, "white")) return rc;
+    if (int rc = use_device(env)) return rc;
+    const uint64_t ply0 = env->ply;
+    env->ply += (uint64_t)n_plies;
+    return with_n(env->n, [&](auto NC) {
+        return launch_play_cnet<decltype(NC)::value>(env, OTH_PLAY_SEARCH_PLAY, black, white, n_plies, nullptr, nullptr,
+                                                     nullptr, actions, rewards, dones, nullptr, ply0,
+                                                     (hipStream_t)stream);
+    });
+}
+
+int oth_reset_vs_cnet(oth_env* env, const oth_cnet_policy* opponent, const int8_t* protagonist, const uint8_t* mask,
+                      oth_stream_t stream) {
+    if (!env) return fail(OTH_EINVAL, "NULL oth_env");
+    if (int rc = check_cnet_policy(opponent, "opponent")) return rc;
+    if (int rc = check_cnet_policy_size(env, opponent, "opponent")) return rc;
+    if (int rc = use_device(env)) return rc;
+    const uint64_t call = env->ply++;
+    return with_n(env->n, [&](auto NC) {
+        return launch_play_cnet<decltype(NC)::value>(env, OTH_PLAY_SEARCH_RESET_VS, opponent, opponent, 0, nullptr,
+                                                     protagonist, mask, nullptr, nullptr, nullptr, nullptr, call,
+                                                     (hipStream_t)stream);
+    });
+}
+
+int oth_step_vs_cnet(oth_env* env, const oth_cnet_policy* opponent, const int32_t* actions, const int8_t* protagonist,
+                     int32_t* rewards, uint8_t* dones, int32_t* plies, oth_stream_t stream) {
+    if (!env) return fail(OTH_EINVAL, "NULL oth_env");
+    if (int rc = check_cnet_policy(opponent, "opponent")) return rc;
+    if (!actions) return fail(OTH_EINVAL, "actions is NULL");
+    if (int rc = check_cnet_policy_size(env, opponent, "opponent")) return rc;
+    if (int rc = use_device(env)) return rc;
+    const uint64_t call = env->ply++;
+    return with_n(env->n, [&](auto NC) {
+        return launch_play_cnet<decltype(NC)::value>(env, OTH_PLAY_SEARCH_STEP_VS, opponent, opponent, 0, actions,
+                                                     protagonist, nullptr, nullptr, rewards, dones, plies, call,
+                                                     (hipStream_t)stream);
+    });
+}
+
 int oth_reset_vs(oth_env* env, int32_t opponent_policy, const int8_t* protagonist, const uint8_t* mask,
                  oth_stream_t stream) {
     OTH_CHECK_ENV(env);

@@ -144,6 +144,14 @@ int launch_play_net(oth_env* env, int mode, const oth_net_policy* black, const o
                     const int32_t* act_in, const int8_t* prot, const uint8_t* mask, int32_t* actions, int32_t* rewards,
                     uint8_t* dones, int32_t* plies, uint64_t ctr, hipStream_t st);
 
+// k_play_cnet (oth_play_cnet, oth_reset_vs_cnet, oth_step_vs_cnet) in play_cnet_n.hip, every N, a unit of its own
+// per board size: launch_play_net's arguments with conv nets.  The arguments are checked; the two channel counts
+// are equal.
+template <int N>
+int launch_play_cnet(oth_env* env, int mode, const oth_cnet_policy* black, const oth_cnet_policy* white, int n_plies,
+                     const int32_t* act_in, const int8_t* prot, const uint8_t* mask, int32_t* actions, int32_t* rewards,
+                     uint8_t* dones, int32_t* plies, uint64_t ctr, hipStream_t st);
+
 // k_mcts (oth_mcts) in mcts_n.hip, every N, a unit of its own per board size.  The arguments are checked.
 template <int N>
 int launch_mcts(oth_env* env, const oth_mcts_params* p, void* workspace, int32_t* visits, int32_t* wins2,

@@ -6,9 +6,10 @@ oth_net_pack / oth_net_eval; include/othello_mi355x.h defines it in integers).
     net_features     the network's 3 N*N inputs as a float tensor, for training
     MLPPolicyValue   the float torch module on those features that a learner trains
     DeviceNet.from_module   the one as the other
-    NetPlayer        a DeviceNet as a player: VecOthelloEnv.play_net, and the embedded
-                     opponent of reset_vs / step_vs (oth_play_net, oth_reset_vs_net,
-                     oth_step_vs_net)
+    NetPlayer        a DeviceNet (or a cnet.DeviceConvNet) as a player:
+                     VecOthelloEnv.play_net, and the embedded opponent of reset_vs /
+                     step_vs (oth_play_net, oth_reset_vs_net, oth_step_vs_net; for a
+                     conv net oth_play_cnet, oth_reset_vs_cnet, oth_step_vs_cnet)
 
 A DeviceNet is an evaluator of VecOthelloEnv.puct_search / puct_play whose outputs
 go to the advance as they are (`quantized = True`): no float lies between the
@@ -229,8 +230,9 @@ class DeviceNet(object):
 
 
 class NetPlayer(object):
-    """A network as a player (struct oth_net_policy): the move of a board is the
-    legal square of the largest logit of `net` (a DeviceNet), the lowest square of
+    """A network as a player (struct oth_net_policy, or struct oth_cnet_policy for
+    a conv net): the move of a board is the legal square of the largest logit of
+    `net` (a DeviceNet or a DeviceConvNet; `kind` is "mlp" or "conv"), the lowest square of
     equals, once the board holds at least `sample_discs` discs; with fewer discs it
     is drawn in proportion to the network's priors (Philox purpose 7, keyed by the
     env's seed, its global id and the ply's index: reproducible and shardable).
@@ -241,14 +243,17 @@ class NetPlayer(object):
     nothing."""
 
     def __init__(self, net, sample_discs=0):
-        if not isinstance(net, DeviceNet):
-            raise TypeError("NetPlayer takes a DeviceNet")
+        from .cnet import DeviceConvNet
+        if not isinstance(net, (DeviceNet, DeviceConvNet)):
+            raise TypeError("NetPlayer takes a DeviceNet or a DeviceConvNet")
         if isinstance(sample_discs, bool) or int(sample_discs) != sample_discs:
             raise ValueError("sample_discs must be an integer")
         if not 0 <= int(sample_discs) <= L.OTH_NET_SAMPLE_DISCS_MAX:
             raise ValueError("sample_discs must be in [0, %d]" % L.OTH_NET_SAMPLE_DISCS_MAX)
         self.net, self.sample_discs = net, int(sample_discs)
-        self._struct = L.OthNetPolicy(net.params, net.blob.data_ptr(), net.blob.numel(), self.sample_discs)
+        self.kind = "conv" if isinstance(net, DeviceConvNet) else "mlp"
+        struct = L.OthCnetPolicy if self.kind == "conv" else L.OthNetPolicy
+        self._struct = struct(net.params, net.blob.data_ptr(), net.blob.numel(), self.sample_discs)
 
     def _policy(self, env):
         """The struct, for an env of the net's board size on the net's device."""
@@ -260,5 +265,8 @@ class NetPlayer(object):
         return self._struct
 
     def __repr__(self):
+        if self.kind == "conv":
+            return "NetPlayer(<%d x %d, conv, %d blocks of %d channels>, sample_discs=%d)" % (
+                self.net.board_size, self.net.board_size, self.net.blocks, self.net.channels, self.sample_discs)
         return "NetPlayer(<%d x %d, %d layers of %d>, sample_discs=%d)" % (
             self.net.board_size, self.net.board_size, self.net.layers, self.net.width, self.sample_discs)

@@ -309,7 +309,7 @@ class SearchPolicy(object):
 class NetPolicy(object):
     """A network as a player (no reference counterpart; the frozen-network opponent
     of self-play learners): the move is VecOthelloEnv.play_net's for the board --
-    the legal square of the largest logit of `net` (a DeviceNet), the lowest square
+    the legal square of the largest logit of `net` (a DeviceNet or a DeviceConvNet), the lowest square
     of equals, and a draw from the priors while the board holds fewer than
     `sample_discs` discs.  The move is computed by the same kernel: the board is
     copied to a one-board scratch env, which plays one ply of NetPlayer(net,

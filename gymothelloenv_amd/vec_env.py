@@ -370,7 +370,9 @@ class VecOthelloEnv(object):
         -- in one launch that never synchronises the host: the argmax of the logits
         over the stored legal squares, or a draw from the priors while the board has
         fewer than the player's sample_discs discs.  The two networks must have the
-        same width.  Random-opening plies, terminated boards, auto-reset, the tallies
+        same width.  With conv players (NetPlayer of a DeviceConvNet) the call is
+        oth_play_cnet: the two must have the same channel count, and an MLP on one
+        side with a conv net on the other is a ValueError.  Random-opening plies, terminated boards, auto-reset, the tallies
         and the ply counter are step_policy's.
 
         Returns (actions, rewards, dones) of shape (n_plies, E) (None if not
@@ -381,13 +383,20 @@ class VecOthelloEnv(object):
         n_plies = int(n_plies)
         if n_plies < 1:
             raise ValueError("n_plies must be >= 1")
+        if white is not None and white.kind != black.kind:
+            raise ValueError("play_net takes two networks of one kind: an MLP against a conv net is not supported")
+        conv = black.kind == "conv"
+        if conv and white is not None and white.net.channels != black.net.channels:
+            raise ValueError("the two conv nets of play_net must have the same channels (%d and %d)" % (
+                black.net.channels, white.net.channels))
         pb = black._policy(self)
         pw = pb if white is None or white is black else white._policy(self)
         a = r = d = None
         if record:
             a, r, d = self._i32(n_plies, self.num_envs), self._i32(n_plies, self.num_envs), self._u8(n_plies, self.num_envs)
-        L.check(self._lib.oth_play_net(self._h, ctypes.addressof(pb), ctypes.addressof(pw), n_plies, _ptr(a), _ptr(r),
-                                       _ptr(d), self._stream()), "oth_play_net")
+        call, what = (self._lib.oth_play_cnet, "oth_play_cnet") if conv else (self._lib.oth_play_net, "oth_play_net")
+        L.check(call(self._h, ctypes.addressof(pb), ctypes.addressof(pw), n_plies, _ptr(a), _ptr(r), _ptr(d),
+                     self._stream()), what)
         return a, r, d
 
     # ------------------------------------------- OthelloEnv semantics on device
@@ -408,13 +417,15 @@ class VecOthelloEnv(object):
         replies until the protagonist (+1 white, the reference default, or -1
         black; int or per-board tensor) is to move.  `opponent` may be a
         SearchConfig: the opponent then plays its searched move (oth_reset_vs_search);
-        or a NetPlayer: it plays its network's move (oth_reset_vs_net)."""
+        or a NetPlayer: it plays its network's move (oth_reset_vs_net, or
+        oth_reset_vs_cnet for a conv net)."""
         from .net import NetPlayer
         prot = self._protagonist(protagonist)
         m = None if mask is None else mask.to(device=self.device, dtype=torch.uint8).contiguous()
         if isinstance(opponent, NetPlayer):
-            L.check(self._lib.oth_reset_vs_net(self._h, ctypes.addressof(opponent._policy(self)), _ptr(prot), _ptr(m),
-                                               self._stream()), "oth_reset_vs_net")
+            call, what = ((self._lib.oth_reset_vs_cnet, "oth_reset_vs_cnet") if opponent.kind == "conv" else
+                          (self._lib.oth_reset_vs_net, "oth_reset_vs_net"))
+            L.check(call(self._h, ctypes.addressof(opponent._policy(self)), _ptr(prot), _ptr(m), self._stream()), what)
             return self.get_observation()
         if isinstance(opponent, SearchConfig):
             L.check(self._lib.oth_reset_vs_search(self._h, ctypes.addressof(opponent._policy(self)), _ptr(prot),
@@ -440,7 +451,8 @@ class VecOthelloEnv(object):
         search ran over max_nodes and were played by GreedyPolicy (int32 (E,)).
 
         `opponent` may be a NetPlayer: the opponent plays its network's move
-        (oth_step_vs_net, one launch, no host round trip per reply) and the
+        (oth_step_vs_net, or oth_step_vs_cnet for a conv net: one launch, no host
+        round trip per reply) and the
         observation comes from an observe launch after it; fallbacks=True raises."""
         from .net import NetPlayer
         prot = self._protagonist(protagonist)
@@ -454,8 +466,10 @@ class VecOthelloEnv(object):
             o = None
             if observe:
                 lay, o = self._obs_out(obs_layout, obs_dtype, obs)
-            L.check(self._lib.oth_step_vs_net(self._h, ctypes.addressof(opponent._policy(self)), _ptr(a), _ptr(prot),
-                                              _ptr(r), _ptr(d), _ptr(n), self._stream()), "oth_step_vs_net")
+            call, what = ((self._lib.oth_step_vs_cnet, "oth_step_vs_cnet") if opponent.kind == "conv" else
+                          (self._lib.oth_step_vs_net, "oth_step_vs_net"))
+            L.check(call(self._h, ctypes.addressof(opponent._policy(self)), _ptr(a), _ptr(prot), _ptr(r), _ptr(d),
+                         _ptr(n), self._stream()), what)
             if observe:
                 L.check(self._lib.oth_observe(self._h, lay, _DTYPES[o.dtype], _ptr(o), self._stream()), "oth_observe")
             return o, r, d.view(torch.bool), n

@@ -118,7 +118,7 @@ enum {
  *     times 2^-24.
  *     Purposes 4 (oth_puct_pick), 5 (oth_replay_sample), 6 (oth_puct_noise)
  *     and 7 (the network's sampled move: oth_play_net, oth_reset_vs_net,
- *     oth_step_vs_net) are stated with those calls.
+ *     oth_step_vs_net and their _cnet twins) are stated with those calls.
  *   - random-opening lengths: three murmur3 32-bit finalisers (fmix32),
  *       key = fmix32(seed lo ^ fmix32(seed hi ^ purpose * 0x7FEB352D)),
  *       word = fmix32(fmix32(key ^ ply lo ^ ply hi * 0x9E3779B9) ^ id),
@@ -1289,6 +1289,46 @@ int oth_reset_vs_net(oth_env *env, const oth_net_policy *opponent, const int8_t 
                      oth_stream_t stream);
 int oth_step_vs_net(oth_env *env, const oth_net_policy *opponent, const int32_t *actions, const int8_t *protagonist,
                     int32_t *rewards, uint8_t *dones, int32_t *plies, oth_stream_t stream);
+
+/* The convolutional network as a player: one colour's (or the embedded
+ * opponent's) move chooser is an oth_cnet network.  The struct is host memory,
+ * read during the call, as oth_net_policy is.
+ *
+ * The network's move is P(board, p) above, word for word, with "z and prior[]
+ * are oth_cnet_eval's logits and priors of the row" in place of oth_net_eval's:
+ * the same M, the same D, the same argmax and tie rule, the same draw (purpose
+ * 7, counter words (id, g lo, g hi, 7), r = floor(u P / 2^32), the first square
+ * whose cumulative prior exceeds r). */
+typedef struct oth_cnet_policy {
+    oth_cnet_params params;  /* as oth_cnet_eval takes them */
+    const void *blob;        /* DEVICE: oth_cnet_pack's bytes, 16-byte aligned */
+    uint64_t blob_bytes;     /* at least what oth_cnet_blob_bytes reports */
+    int32_t sample_discs;    /* [0, OTH_NET_SAMPLE_DISCS_MAX] */
+} oth_cnet_policy;
+
+/* oth_play_cnet / oth_reset_vs_cnet / oth_step_vs_cnet are oth_play_net /
+ * oth_reset_vs_net / oth_step_vs_net with that P: everything the comment on
+ * oth_play_net states beside the move -- random-opening plies, terminated
+ * boards, the empty stored mask's action -1, OTH_AUTO_RESET, both tallies, the
+ * ply counter, the graph region's offset, the vs calls' phase order and their
+ * c*256 + j counters -- holds unchanged.  The two networks of oth_play_cnet may
+ * differ in blocks, in every shift and in the weights; they must have the same
+ * `channels` (the kernel's compile-time parameter): another count is OTH_EINVAL.
+ *
+ * One launch each (a workgroup of four waves per 4, 2 or 1 boards: the board's
+ * activations stay in its LDS); no call synchronises the host.  OTH_EINVAL,
+ * checked before the handle's device is touched and with nothing launched: the
+ * list of oth_play_net, with oth_cnet_eval's field ranges, oth_cnet_blob_bytes
+ * for blob_bytes and "two channel counts" for "two widths".  A blob packed for
+ * another geometry or other shifts (any of its first 32 bytes: both tags and the
+ * 16 block shifts) is found by the kernel, which then changes nothing -- no
+ * board, no output, no tally; the ply counter has advanced all the same. */
+int oth_play_cnet(oth_env *env, const oth_cnet_policy *black, const oth_cnet_policy *white, int32_t n_plies,
+                  int32_t *actions, int32_t *rewards, uint8_t *dones, oth_stream_t stream);
+int oth_reset_vs_cnet(oth_env *env, const oth_cnet_policy *opponent, const int8_t *protagonist, const uint8_t *mask,
+                      oth_stream_t stream);
+int oth_step_vs_cnet(oth_env *env, const oth_cnet_policy *opponent, const int32_t *actions, const int8_t *protagonist,
+                     int32_t *rewards, uint8_t *dones, int32_t *plies, oth_stream_t stream);
 
 /* possible_moves of every env as masks uint64[E][W] (othello.py:242, :270, :466). */
 int oth_legal(oth_env *env, uint64_t *out, oth_stream_t stream);
