@@ -9,7 +9,7 @@ terminal/score) as HIP kernels for gfx950 behind a C ABI
     SimpleOthelloEnv,        reference's constructor / attributes / 4-tuple step
     OthelloEnv
     RandomPolicy, GreedyPolicy, MaxiMinPolicy, MonteCarloPolicy, MCTSPolicy, PUCTPolicy,
-    SolverPolicy, SearchPolicy, NetPolicy,
+    SolverPolicy, SearchPolicy, NetPolicy, NTuplePolicy,
     make_state, undo_state
     default_search_weights   the conventional square weights of VecOthelloEnv.search
     SearchConfig             a search as a player: VecOthelloEnv.play_search, and the
@@ -32,6 +32,9 @@ terminal/score) as HIP kernels for gfx950 behind a C ABI
                                      the float module a learner trains: an evaluator and a player as a DeviceNet is
     RootNoise, dirichlet_table       Dirichlet root noise for self-play, drawn on the device in integers
                                      (VecOthelloEnv.puct_noise; puct_search / puct_play take noise=RootNoise(...))
+    NTupleNet, snake_tuples,         the n-tuple network (oth_ntuple_eval, oth_ntuple_update): look-up tables over
+    ntuple_evaluator                 small sets of squares that evaluate and learn on the device in integers, the
+                                     evaluation of VecOthelloEnv.search_ntuple and an evaluator of puct_search
 """
 from ._lib import LIB_PATH, OthelloLibError, load  # noqa: F401
 
@@ -54,11 +57,14 @@ def __getattr__(name):
     if name in ("RootNoise", "dirichlet_table"):
         from . import noise
         return getattr(noise, name)
+    if name in ("NTupleNet", "snake_tuples", "ntuple_evaluator"):
+        from . import ntuple
+        return getattr(ntuple, name)
     if name in ("OthelloBaseEnv", "SimpleOthelloEnv", "OthelloEnv"):
         from . import othello
         return getattr(othello, name)
     if name in ("RandomPolicy", "GreedyPolicy", "MaxiMinPolicy", "MonteCarloPolicy", "MCTSPolicy",
-                "PUCTPolicy", "SolverPolicy", "SearchPolicy", "NetPolicy"):
+                "PUCTPolicy", "SolverPolicy", "SearchPolicy", "NetPolicy", "NTuplePolicy"):
         from . import policies
         return getattr(policies, name)
     if name in ("masked_sample", "masked_log_prob"):

@@ -57,6 +57,8 @@ OTH_NET_MAX_LAYERS, OTH_NET_MAX_WIDTH, OTH_NET_MAX_SHIFT = 4, 512, 24  # oth_net
 OTH_NET_BIAS_MAX, OTH_NET_MAX_ROWS = 1 << 30, 1 << 24
 OTH_NET_SAMPLE_DISCS_MAX = 257
 OTH_CNET_MAX_BLOCKS = 8  # oth_cnet_*
+OTH_NTUPLE_MAX_TUPLES, OTH_NTUPLE_MAX_LENGTH, OTH_NTUPLE_MAX_ROWS = 32, 8, 1 << 24  # oth_ntuple_*
+OTH_NTUPLE_MAX_RATE, OTH_NTUPLE_MAX_RATE_SHIFT = 1 << 24, 40
 OTH_GRAPH_SLOTS = 64
 OTH_GRAPH_COUNTER_SHIFT = 40
 
@@ -160,6 +162,14 @@ class OthCnetParams(ctypes.Structure):
                 ("value_shift", ctypes.c_int32)]
 
 
+class OthNtupleParams(ctypes.Structure):
+    """struct oth_ntuple_params (include/othello_mi355x.h): host memory read during the call."""
+    _fields_ = [("tuples", ctypes.c_int32),
+                ("length", ctypes.c_int32 * 32),
+                ("squares", (ctypes.c_int32 * 8) * 32),
+                ("value_shift", ctypes.c_int32)]
+
+
 class OthNetPolicy(ctypes.Structure):
     """struct oth_net_policy (include/othello_mi355x.h): one colour's network as a
     player, host memory read during the call; `blob` is a device address."""
@@ -219,6 +229,12 @@ SIGNATURES = {
     "oth_cnet_blob_bytes": (_I32, [_I32, _P, _P]),
     "oth_cnet_pack": (_I32, [_I32, _P, _P, _P, _P, _U64]),
     "oth_cnet_eval": (_I32, [_I32, _I32, _P, _P, _U64, _P, _P, _P, _P, _P, _P, _P]),
+    "oth_ntuple_weight_count": (_I32, [_I32, _P, _P]),
+    "oth_ntuple_plan_bytes": (_I32, [_I32, _P, _P]),
+    "oth_ntuple_plan": (_I32, [_I32, _P, _P, _U64]),
+    "oth_ntuple_eval": (_I32, [_I32, _I32, _P, _P, _U64, _P, _U64, _P, _P, _P, _P, _P]),
+    "oth_ntuple_update": (_I32, [_I32, _I32, _P, _P, _U64, _P, _U64, _P, _P, _P, _I32, _I32, _P, _P]),
+    "oth_search_ntuple": (_I32, [_P, _I32, _P, _P, _U64, _P, _U64, _I32, _U64, _P, _P, _P, _P, _P, _P]),
     "oth_play_search": (_I32, [_P, _P, _P, _I32, _P, _P, _P, _P, _P]),
     "oth_reset_vs_search": (_I32, [_P, _P, _P, _P, _P]),
     "oth_step_vs_search": (_I32, [_P, _P, _P, _P, _P, _P, _P, _P, _P]),

@@ -10,7 +10,8 @@ csrc/play_net_n.hip (oth_play_net, oth_reset_vs_net, oth_step_vs_net: the networ
 csrc/play_cnet_n.hip (oth_play_cnet, oth_reset_vs_cnet, oth_step_vs_cnet: the conv net as a player) and
 csrc/mcts_n.hip (oth_mcts) and csrc/puct_n.hip (oth_puct_begin, oth_puct_advance, oth_puct_result, oth_puct_pick,
 oth_puct_reroot) and csrc/replay_n.hip (oth_replay_begin, oth_replay_append, oth_replay_label, oth_replay_counts,
-oth_replay_gather, oth_replay_sample, oth_symmetry_masks) once per N,
+oth_replay_gather, oth_replay_sample, oth_symmetry_masks) and csrc/ntuple_n.hip (oth_ntuple_eval,
+oth_ntuple_update, oth_search_ntuple: the n-tuple network) once per N,
 csrc/net.hip (oth_net_eval: the int8 network on the matrix cores), csrc/cnet.hip (oth_cnet_eval: the int8
 residual convolutional network on the matrix cores) and csrc/noise.hip (oth_puct_noise: Dirichlet root noise in
 integers) once for every N,
@@ -40,7 +41,7 @@ SOURCES = ("capi.hip", "kernels_n.hip", "play_rand_n.hip", "masked.hip", "device
            "solve.hpp", "root_tasks.hpp", "search_n.hip", "search.hpp", "play_search_n.hip", "play_search.hpp",
            "mcts_n.hip", "mcts.hpp", "puct_n.hip", "puct.hpp", "replay_n.hip", "replay.hpp", "net.hip", "net.hpp",
            "noise.hip", "noise.hpp", "net_dev.hpp", "play_owner.hpp", "play_net_n.hip", "play_net.hpp", "cnet.hip",
-           "cnet.hpp", "cnet_dev.hpp", "play_cnet_n.hip", "play_cnet.hpp")
+           "cnet.hpp", "cnet_dev.hpp", "play_cnet_n.hip", "play_cnet.hpp", "ntuple_n.hip", "ntuple.hpp")
 PLAY_SIZES = list(range(4, 12))  # k_play_rand (one-word boards) and k_play_rand_w (two-word boards)
 # play_rand_n.hip: the max-ILP machine scheduler (one wave per SIMD: latency hidden by the schedule
 # counts, occupancy does not); the rest of the library keeps the default scheduler
@@ -140,6 +141,8 @@ def build(force=False, verbose=True, extra_flags=(), out=OUT, jobs=None, only_si
               for n in SIZES]
     units += [(os.path.join(CSRC, "replay_n.hip"), os.path.join(objdir, "replay_n%d.o" % n), ["-DOTH_N=%d" % n])
               for n in SIZES]
+    units += [(os.path.join(CSRC, "ntuple_n.hip"), os.path.join(objdir, "ntuple_n%d.o" % n), ["-DOTH_N=%d" % n])
+              for n in SIZES]
 
     def compile_one(u):
         src, obj, defs = u
@@ -161,7 +164,7 @@ def build(force=False, verbose=True, extra_flags=(), out=OUT, jobs=None, only_si
             "playouts_n%d.o" % n for n in only_sizes} | {"solve_n%d.o" % n for n in only_sizes} | {
             "search_n%d.o" % n for n in only_sizes} | {"play_search_n%d.o" % n for n in only_sizes} | {"play_net_n%d.o" % n for n in only_sizes} | {"play_cnet_n%d.o" % n for n in only_sizes} | {
             "mcts_n%d.o" % n for n in only_sizes} | {"puct_n%d.o" % n for n in only_sizes} | {
-            "replay_n%d.o" % n for n in only_sizes}
+            "replay_n%d.o" % n for n in only_sizes} | {"ntuple_n%d.o" % n for n in only_sizes}
     if only_sizes is not None or only_units is not None:
         reuse = [os.path.join(OBJDIR, os.path.basename(u[1])) for u in units if os.path.basename(u[1]) not in keep]
         units = [u for u in units if os.path.basename(u[1]) in keep]

@@ -13,6 +13,7 @@
 #include "launch.hpp"
 #include "net.hpp"
 #include "cnet.hpp"
+#include "ntuple.hpp"
 
 using namespace oth;
 using namespace oth_host;
@@ -877,6 +878,121 @@ int oth_search(oth_env* env, int32_t depth, const int8_t* weights, int32_t mobil
         return launch_search<decltype(NC)::value>(env, depth, weights, mobility_weight, terminal_weight,
                                                   (uint32_t)max_nodes, value, best, move_values, status, nodes,
                                                   (hipStream_t)stream);
+    });
+}
+
+}  // extern "C"
+
+namespace {
+static_assert(sizeof(oth_ntuple_params) == sizeof(NtupleParams), "ntuple.hpp's NtupleParams is the header's struct");
+
+// oth_ntuple_params as ntuple.hpp's NtupleParams, checked: what every oth_ntuple call does first
+int ntuple_params(int32_t board_size, const oth_ntuple_params* params, NtupleParams* out) {
+    if (!params) return fail(OTH_EINVAL, "params is NULL");
+    memcpy(out, params, sizeof(*out));
+    if (const char* why = ntuple_check(board_size, out)) return fail(OTH_EINVAL, why);
+    return OTH_OK;
+}
+
+// the plan and the weights of a device call, against the parameters
+int ntuple_device_args(const NtupleParams& np, const void* plan, uint64_t plan_bytes, const void* weights,
+                       uint64_t weight_count) {
+    if (!plan) return fail(OTH_EINVAL, "plan is NULL");
+    if (!weights) return fail(OTH_EINVAL, "weights is NULL");
+    if (reinterpret_cast<uintptr_t>(plan) & 7u) return fail(OTH_EINVAL, "plan must be 8-byte aligned");
+    if (plan_bytes < ntuple_plan_bytes(np)) return fail(OTH_EINVAL, "plan_bytes is below what oth_ntuple_plan_bytes reports");
+    if (weight_count < (uint64_t)ntuple_n_weights(np) + 1u)
+        return fail(OTH_EINVAL, "weight_count is below what oth_ntuple_weight_count reports");
+    return OTH_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int oth_ntuple_weight_count(int32_t board_size, const oth_ntuple_params* params, uint64_t* count) {
+    if (!count) return fail(OTH_EINVAL, "count is NULL");
+    NtupleParams np;
+    if (int rc = ntuple_params(board_size, params, &np)) return rc;
+    *count = (uint64_t)ntuple_n_weights(np) + 1u;
+    return OTH_OK;
+}
+
+int oth_ntuple_plan_bytes(int32_t board_size, const oth_ntuple_params* params, uint64_t* bytes) {
+    if (!bytes) return fail(OTH_EINVAL, "bytes is NULL");
+    NtupleParams np;
+    if (int rc = ntuple_params(board_size, params, &np)) return rc;
+    *bytes = ntuple_plan_bytes(np);
+    return OTH_OK;
+}
+
+int oth_ntuple_plan(int32_t board_size, const oth_ntuple_params* params, void* plan, uint64_t plan_bytes) {
+    if (!plan) return fail(OTH_EINVAL, "plan is NULL");
+    NtupleParams np;
+    if (int rc = ntuple_params(board_size, params, &np)) return rc;
+    if (reinterpret_cast<uintptr_t>(plan) & 7u) return fail(OTH_EINVAL, "plan must be 8-byte aligned");
+    if (plan_bytes < ntuple_plan_bytes(np)) return fail(OTH_EINVAL, "plan_bytes is below what oth_ntuple_plan_bytes reports");
+    ntuple_plan(board_size, np, static_cast<uint32_t*>(plan));
+    return OTH_OK;
+}
+
+int oth_ntuple_eval(int32_t board_size, int32_t n_rows, const oth_ntuple_params* params, const void* plan,
+                    uint64_t plan_bytes, const int32_t* weights, uint64_t weight_count, const uint64_t* boards,
+                    const uint16_t* meta, int32_t* values, int64_t* sums, oth_stream_t stream) {
+    if (!boards || !meta) return fail(OTH_EINVAL, "boards or meta is NULL");
+    if (!values) return fail(OTH_EINVAL, "values is NULL");
+    NtupleParams np;
+    if (int rc = ntuple_params(board_size, params, &np)) return rc;
+    if (int rc = ntuple_device_args(np, plan, plan_bytes, weights, weight_count)) return rc;
+    if (n_rows < 0 || n_rows > OTH_NTUPLE_MAX_ROWS) return fail(OTH_EINVAL, "n_rows must be in [0, 2^24]");
+    if (n_rows == 0) return OTH_OK;
+    const NtupleKey key = ntuple_key(board_size, np);
+    return with_n(board_size, [&](auto NC) {
+        return launch_ntuple_eval<decltype(NC)::value>(n_rows, plan, key, weights, boards, meta, values, sums,
+                                                       (hipStream_t)stream);
+    });
+}
+
+int oth_ntuple_update(int32_t board_size, int32_t n_rows, const oth_ntuple_params* params, const void* plan,
+                      uint64_t plan_bytes, int32_t* weights, uint64_t weight_count, const uint64_t* boards,
+                      const uint16_t* meta, const int32_t* targets, int32_t rate, int32_t rate_shift, int32_t* deltas,
+                      oth_stream_t stream) {
+    if (!boards || !meta) return fail(OTH_EINVAL, "boards or meta is NULL");
+    if (!targets) return fail(OTH_EINVAL, "targets is NULL");
+    if (!deltas) return fail(OTH_EINVAL, "deltas is NULL");
+    NtupleParams np;
+    if (int rc = ntuple_params(board_size, params, &np)) return rc;
+    if (int rc = ntuple_device_args(np, plan, plan_bytes, weights, weight_count)) return rc;
+    if (n_rows < 0 || n_rows > OTH_NTUPLE_MAX_ROWS) return fail(OTH_EINVAL, "n_rows must be in [0, 2^24]");
+    if (rate < 0 || rate > OTH_NTUPLE_MAX_RATE) return fail(OTH_EINVAL, "rate must be in [0, 2^24]");
+    if (rate_shift < 0 || rate_shift > OTH_NTUPLE_MAX_RATE_SHIFT) return fail(OTH_EINVAL, "rate_shift must be in [0, 40]");
+    if (n_rows == 0) return OTH_OK;
+    const NtupleKey key = ntuple_key(board_size, np);
+    return with_n(board_size, [&](auto NC) {
+        return launch_ntuple_update<decltype(NC)::value>(n_rows, plan, key, weights, boards, meta, targets, rate,
+                                                         rate_shift, deltas, (hipStream_t)stream);
+    });
+}
+
+int oth_search_ntuple(oth_env* env, int32_t depth, const oth_ntuple_params* params, const void* plan,
+                      uint64_t plan_bytes, const int32_t* weights, uint64_t weight_count, int32_t terminal_weight,
+                      uint64_t max_nodes, int32_t* value, int32_t* best, int32_t* move_values, uint8_t* status,
+                      uint64_t* nodes, oth_stream_t stream) {
+    // the argument checks come before the handle's device is touched
+    if (!env) return fail(OTH_EINVAL, "NULL oth_env");
+    if (!value) return fail(OTH_EINVAL, "value is NULL");
+    NtupleParams np;
+    if (int rc = ntuple_params(env->n, params, &np)) return rc;
+    if (int rc = ntuple_device_args(np, plan, plan_bytes, weights, weight_count)) return rc;
+    if (depth < 1 || depth > OTH_SEARCH_MAX_DEPTH) return fail(OTH_EINVAL, "depth must be in [1, 14]");
+    if (terminal_weight < 1 || terminal_weight > 32767)
+        return fail(OTH_EINVAL, "terminal_weight must be in [1, 32767]");
+    if (max_nodes < 1 || max_nodes > 0xffffffffull) return fail(OTH_EINVAL, "max_nodes must be in [1, 2^32 - 1]");
+    if (int rc = use_device(env)) return rc;
+    const NtupleKey key = ntuple_key(env->n, np);
+    return with_n(env->n, [&](auto NC) {
+        return launch_search_ntuple<decltype(NC)::value>(env, depth, plan, key, weights, terminal_weight,
+                                                         (uint32_t)max_nodes, value, best, move_values, status, nodes,
+                                                         (hipStream_t)stream);
     });
 }
 

@@ -44,6 +44,10 @@ struct oth_env {
     uint32_t rec_seq;         // the last record's sequence number
 };
 
+namespace oth {
+struct NtupleKey;  // ntuple.hpp
+}
+
 namespace oth_host {
 
 // error reporting (capi.hip): set the thread's oth_last_error() and return the code
@@ -247,5 +251,20 @@ int launch_cnet_eval(int n, const oth_cnet_params* p, int n_rows, const void* bl
 int launch_puct_noise(oth_env* env, int rows_per_board, const uint8_t* kind, const uint64_t* boards,
                       const int32_t* priors_in, int32_t* priors_out, int epsilon, const uint32_t* table, uint64_t seed,
                       uint32_t id_key, uint64_t counter, hipStream_t st);
+
+// k_ntuple_eval (oth_ntuple_eval), k_ntuple_delta + k_ntuple_add (oth_ntuple_update) and k_search_ntuple
+// (oth_search_ntuple) in ntuple_n.hip, every N, a unit of its own per board size.  The arguments are checked,
+// n_rows >= 1; key: what the plan's header must hold (ntuple.hpp).
+template <int N>
+int launch_ntuple_eval(int n_rows, const void* plan, const oth::NtupleKey& key, const int32_t* weights,
+                       const uint64_t* boards, const uint16_t* meta, int32_t* values, int64_t* sums, hipStream_t st);
+template <int N>
+int launch_ntuple_update(int n_rows, const void* plan, const oth::NtupleKey& key, int32_t* weights,
+                         const uint64_t* boards, const uint16_t* meta, const int32_t* targets, int32_t rate,
+                         int rate_shift, int32_t* deltas, hipStream_t st);
+template <int N>
+int launch_search_ntuple(oth_env* env, int depth, const void* plan, const oth::NtupleKey& key, const int32_t* weights,
+                         int terminal, uint32_t max_nodes, int32_t* value, int32_t* best, int32_t* move_values,
+                         uint8_t* status, uint64_t* nodes, hipStream_t st);
 
 }  // namespace oth_host

@@ -306,6 +306,34 @@ class SearchPolicy(object):
         return self.get_action(obs)
 
 
+class NTuplePolicy(object):
+    """Depth-limited alpha-beta over an n-tuple network (no reference counterpart: the
+    learned counterpart of SearchPolicy): the move is oth_search_ntuple's `best` at
+    `depth` over `net` (an ntuple.NTupleNet), a game end valued by `terminal`.  Where
+    the search runs over its node budget (ABORTED) GreedyPolicy moves, as for
+    SearchPolicy."""
+
+    def __init__(self, net, depth=1, terminal=64):
+        self.env = None
+        self.net, self.depth, self.terminal = net, int(depth), int(terminal)
+        self.fallback = GreedyPolicy()
+
+    def reset(self, env):
+        self.env = _base(env)
+        self.fallback.reset(env)
+
+    def get_action(self, obs):
+        vec = self.env._vec
+        self.env._sync()
+        best, status = vec.search_ntuple(self.depth, self.net, terminal=self.terminal, best=True, status=True)[1:]
+        if int(status.cpu()[0]) == L.OTH_SEARCH_DONE:
+            return int(best.cpu()[0])
+        return self.fallback.get_action(obs)
+
+    def get_test_action(self, obs):
+        return self.get_action(obs)
+
+
 class NetPolicy(object):
     """A network as a player (no reference counterpart; the frozen-network opponent
     of self-play learners): the move is VecOthelloEnv.play_net's for the board --
@@ -347,4 +375,4 @@ class NetPolicy(object):
         return self.get_action(obs)
 
 
-__all__ = ['RandomPolicy', 'GreedyPolicy', 'MaxiMinPolicy', 'MonteCarloPolicy', 'MCTSPolicy', 'PUCTPolicy', 'SolverPolicy', 'SearchPolicy', 'NetPolicy', 'PROTAGONIST_TURN', 'OPPONENT_TURN', 'WHITE_DISK']
+__all__ = ['RandomPolicy', 'GreedyPolicy', 'MaxiMinPolicy', 'MonteCarloPolicy', 'MCTSPolicy', 'PUCTPolicy', 'SolverPolicy', 'SearchPolicy', 'NTuplePolicy', 'NetPolicy', 'PROTAGONIST_TURN', 'OPPONENT_TURN', 'WHITE_DISK']

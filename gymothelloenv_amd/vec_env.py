@@ -1462,6 +1462,35 @@ class VecOthelloEnv(object):
             kw.pop(k, None)
         return self.search(best=True, **kw)[1]
 
+    def search_ntuple(self, depth, net, terminal=64, max_nodes=1 << 22, best=False, move_values=False, status=False,
+                      nodes=False):
+        """search() with a learned evaluation (oth_search_ntuple): the frontier is
+        valued by `net` (an ntuple.NTupleNet for this board size on this device), its
+        value from the side to move there, in [-32768, 32768]; a game end by terminal
+        * (my discs - their discs).  Everything else -- rules, outputs, statuses,
+        nodes, determinism -- is search()'s.  The net's weights are read as they are
+        when the launch runs."""
+        net._check_env(self)
+        E, nn = self.num_envs, self.board_size * self.board_size
+        val = self._i32(E)
+        bt = self._i32(E) if best else None
+        mv = self._i32(E, nn) if move_values else None
+        stt = self._u8(E) if status else None
+        nd = torch.empty(E, dtype=torch.int64, device=self.device) if nodes else None
+        L.check(self._lib.oth_search_ntuple(self._h, int(depth), ctypes.byref(net.params), _ptr(net.plan),
+                                            net.plan_bytes, _ptr(net._weights()), net.weight_count, int(terminal),
+                                            int(max_nodes), _ptr(val), _ptr(bt), _ptr(mv), _ptr(stt), _ptr(nd),
+                                            self._stream()), "oth_search_ntuple")
+        res = (val,) + tuple(t for t in (bt, mv, stt, nd) if t is not None)
+        return res[0] if len(res) == 1 else res
+
+    def search_ntuple_actions(self, **kw):
+        """Every board's best move of search_ntuple (its `best`): int32 (E,), -1 where
+        the search gives none."""
+        for k in ("best", "move_values", "status", "nodes"):
+            kw.pop(k, None)
+        return self.search_ntuple(best=True, **kw)[1]
+
     def _sampler_inputs(self, logits, uniforms):
         """(logits rows, uniforms) checked before a launch reads them: the rows on
         this handle's device, one per board; uniforms float32 on it, >= E of them."""

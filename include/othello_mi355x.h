@@ -1070,6 +1070,112 @@ int oth_net_eval(int32_t board_size, int32_t n_rows, const oth_net_params *param
                  uint64_t blob_bytes, const uint64_t *boards, const uint16_t *meta, const uint64_t *legal,
                  int32_t *priors, int32_t *values, int32_t *logits, oth_stream_t stream);
 
+/* The n-tuple network: a sum of look-up tables indexed by the contents of small
+ * sets of squares, applied under the eight board symmetries and trained by a
+ * delta rule (no reference counterpart: the learned evaluation of the
+ * Othello-learning literature, where oth_search's weighted piece counter is
+ * the hand-made one).  It evaluates rows in the exchange format, learns from
+ * them, and sits at the frontier of the alpha-beta search.  Everything is an
+ * exact integer function of its inputs; the training step is a scatter-add of
+ * integers and so does not depend on any order.
+ *
+ * Geometry.  N is the board size, nn = N N, W the words of a board, sigma_s
+ * (s in [0, 8)) the symmetry defined for oth_replay_gather above.
+ *
+ * Parameters (struct oth_ntuple_params, host memory read during the call, named
+ * in every call): tuples = T in [1, OTH_NTUPLE_MAX_TUPLES]; length[t] = l_t in
+ * [1, OTH_NTUPLE_MAX_LENGTH] for t < T; squares[t][i] = q_{t,i} in [0, nn) for
+ * i < l_t, distinct within a tuple; value_shift in [0, 24].  Fields beyond T or
+ * l_t are not read.
+ *
+ * Weights.  A device array int32[n_weights + 1], n_weights = sum_t 3^l_t.  Tuple
+ * t's table starts at off_t = sum_{u < t} 3^l_u; the last element is the bias.
+ * They are a plain array, part of no packed blob: the learner owns them.
+ *
+ * One row is boards uint64[2W] (black words, then white) and meta uint16; the
+ * mover's words M are the white words if meta bit 0 is set, else the black
+ * words, the other colour's are O.  Every other meta bit and bits at or above
+ * nn are never read.
+ *   cell code  c(a) = 1 if a in M, else 2 if a in O, else 0 (M wins on a square
+ *              set in both: no index leaves its table on an unreachable row).
+ *   index      idx_{t,s} = sum_{i < l_t} 3^i c(sigma_s(q_{t,i})).
+ *   sum        S = bias + sum_t sum_{s < 8} w[off_t + idx_{t,s}], an int64.  A
+ *              tuple that a symmetry maps onto itself hits one entry more than
+ *              once, and every hit counts.
+ *   value      clamp(S >> value_shift, -32768, 32768), an arithmetic shift: from
+ *              the mover's side, in units of 1 / OTH_PUCT_VALUE_ONE -- what
+ *              oth_puct_advance takes as `values`.
+ *
+ * oth_ntuple_weight_count: n_weights + 1.  Needs no GPU.
+ * oth_ntuple_plan_bytes, oth_ntuple_plan: host memory to host memory, like
+ * oth_net_pack; they validate every range above.  The plan holds the 8 T
+ * transformed square lists, the offsets and a header that identifies
+ * (board_size, params); it is the library's, opaque, and holds no addresses, so
+ * a byte copy to the device is all that is needed (plan 8-byte aligned, there
+ * and here).  A call that names another geometry or other parameters than the
+ * plan was made for writes nothing.
+ *
+ * oth_ntuple_eval.  boards uint64[R][2W], meta uint16[R], plan and weights are
+ * device inputs, R = n_rows in [0, OTH_NTUPLE_MAX_ROWS]; values int32[R] is
+ * written; sums int64[R] (S) may be NULL.  Rows are independent of each other
+ * and of how they are batched.  One launch (none for R = 0); the call keeps no
+ * state, never synchronises and is capturable into a HIP graph.
+ *
+ * oth_ntuple_update: one delta-rule step on the R rows, with batch semantics.
+ * With v_r the value of row r under the weights as they are before the call,
+ *   d_r = clamp(round((clamp(targets[r], -32768, 32768) - v_r) rate),
+ *               -2^30, 2^30),
+ * round(x) = (x + 2^(rate_shift - 1)) >> rate_shift in int64 for rate_shift >=
+ * 1 and x for rate_shift 0; rate in [0, OTH_NTUPLE_MAX_RATE], rate_shift in [0,
+ * OTH_NTUPLE_MAX_RATE_SHIFT].  (Round to nearest, not a truncating shift: that
+ * one gives 0 for small positive errors and -1 for small negative ones, and the
+ * weights drift.)  Afterwards every one of the 8 T entries a row hits has had
+ * d_r added once per hit, and the bias once; sums over rows are taken modulo
+ * 2^32 in two's complement.  deltas int32[R] (d_r) is required and written.
+ * Two launches in stream order: the first computes every d_r from the old
+ * weights, the second adds with device-scope relaxed atomics on uint32.
+ * Integer addition commutes: the weights afterwards do not depend on the order
+ * of arrival or the mapping.  targets int32[R] is a device input.
+ *
+ * oth_search_ntuple: oth_search's contract word for word -- rules, statuses,
+ * nodes, the root's stored possible_moves, determinism, outputs -- but for rule
+ * 2: the frontier's H(M, O) is the value above of the row (M to move against
+ * O).  |value| <= 2^15 and |T| <= 32767 * 256 < 2^23 keep every value strictly
+ * inside (-2^24, 2^24).  H is not antisymmetric in general: it is taken from the
+ * side to move at the frontier, whoever placed the last disc.
+ *
+ * OTH_EINVAL, with nothing launched or written: NULL required pointers, a
+ * board size or a field of params out of range, plan_bytes below what
+ * oth_ntuple_plan_bytes reports, a plan that is not 8-byte aligned,
+ * weight_count below what oth_ntuple_weight_count reports, n_rows, rate,
+ * rate_shift, depth, terminal_weight or max_nodes out of range (the search's
+ * as oth_search's).  Every board size works. */
+#define OTH_NTUPLE_MAX_TUPLES     32
+#define OTH_NTUPLE_MAX_LENGTH     8
+#define OTH_NTUPLE_MAX_ROWS       (1 << 24)
+#define OTH_NTUPLE_MAX_RATE       (1 << 24)
+#define OTH_NTUPLE_MAX_RATE_SHIFT 40
+typedef struct oth_ntuple_params {
+    int32_t tuples;          /* T in [1, 32] */
+    int32_t length[32];      /* l_t in [1, 8], t < T */
+    int32_t squares[32][8];  /* q_{t,i} in [0, N*N), i < l_t, distinct within a tuple */
+    int32_t value_shift;     /* in [0, 24] */
+} oth_ntuple_params;
+int oth_ntuple_weight_count(int32_t board_size, const oth_ntuple_params *params, uint64_t *count);
+int oth_ntuple_plan_bytes(int32_t board_size, const oth_ntuple_params *params, uint64_t *bytes);
+int oth_ntuple_plan(int32_t board_size, const oth_ntuple_params *params, void *plan, uint64_t plan_bytes);
+int oth_ntuple_eval(int32_t board_size, int32_t n_rows, const oth_ntuple_params *params, const void *plan,
+                    uint64_t plan_bytes, const int32_t *weights, uint64_t weight_count, const uint64_t *boards,
+                    const uint16_t *meta, int32_t *values, int64_t *sums, oth_stream_t stream);
+int oth_ntuple_update(int32_t board_size, int32_t n_rows, const oth_ntuple_params *params, const void *plan,
+                      uint64_t plan_bytes, int32_t *weights, uint64_t weight_count, const uint64_t *boards,
+                      const uint16_t *meta, const int32_t *targets, int32_t rate, int32_t rate_shift, int32_t *deltas,
+                      oth_stream_t stream);
+int oth_search_ntuple(oth_env *env, int32_t depth, const oth_ntuple_params *params, const void *plan,
+                      uint64_t plan_bytes, const int32_t *weights, uint64_t weight_count, int32_t terminal_weight,
+                      uint64_t max_nodes, int32_t *value, int32_t *best, int32_t *move_values, uint8_t *status,
+                      uint64_t *nodes, oth_stream_t stream);
+
 /* The convolutional network: an int8 residual 3 x 3 convolutional policy-value
  * network on the same rows, with the same outputs and under the same contract as
  * oth_net_* above: every output is an exact integer function of the row, the
