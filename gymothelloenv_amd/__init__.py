@@ -35,6 +35,10 @@ terminal/score) as HIP kernels for gfx950 behind a C ABI
     NTupleNet, snake_tuples,         the n-tuple network (oth_ntuple_eval, oth_ntuple_update): look-up tables over
     ntuple_evaluator                 small sets of squares that evaluate and learn on the device in integers, the
                                      evaluation of VecOthelloEnv.search_ntuple and an evaluator of puct_search
+    NTuplePlayer, TDRows             an NTupleNet as a player: VecOthelloEnv.play_ntuple (with the TD(0) rows of
+                                     its plies from the same launch), the opponent of reset_vs / step_vs, and
+                                     NTupleNet.td_play, a TD round in two calls (oth_play_ntuple,
+                                     oth_ntuple_update_masked)
 """
 from ._lib import LIB_PATH, OthelloLibError, load  # noqa: F401
 
@@ -57,7 +61,7 @@ def __getattr__(name):
     if name in ("RootNoise", "dirichlet_table"):
         from . import noise
         return getattr(noise, name)
-    if name in ("NTupleNet", "snake_tuples", "ntuple_evaluator"):
+    if name in ("NTupleNet", "snake_tuples", "ntuple_evaluator", "NTuplePlayer", "TDRows"):
         from . import ntuple
         return getattr(ntuple, name)
     if name in ("OthelloBaseEnv", "SimpleOthelloEnv", "OthelloEnv"):

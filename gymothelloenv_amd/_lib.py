@@ -59,6 +59,7 @@ OTH_NET_SAMPLE_DISCS_MAX = 257
 OTH_CNET_MAX_BLOCKS = 8  # oth_cnet_*
 OTH_NTUPLE_MAX_TUPLES, OTH_NTUPLE_MAX_LENGTH, OTH_NTUPLE_MAX_ROWS = 32, 8, 1 << 24  # oth_ntuple_*
 OTH_NTUPLE_MAX_RATE, OTH_NTUPLE_MAX_RATE_SHIFT = 1 << 24, 40
+OTH_NTUPLE_EXPLORE_ONE = 65536  # oth_ntuple_policy.explore: epsilon in 1 / 65536
 OTH_GRAPH_SLOTS = 64
 OTH_GRAPH_COUNTER_SHIFT = 40
 
@@ -188,6 +189,31 @@ class OthCnetPolicy(ctypes.Structure):
                 ("sample_discs", ctypes.c_int32)]
 
 
+class OthNtuplePolicy(ctypes.Structure):
+    """struct oth_ntuple_policy (include/othello_mi355x.h): one colour's n-tuple network
+    as a player, host memory read during the call; `plan` and `weights` are device
+    addresses."""
+    _fields_ = [("params", OthNtupleParams),
+                ("plan", ctypes.c_void_p),
+                ("plan_bytes", ctypes.c_uint64),
+                ("weights", ctypes.c_void_p),
+                ("weight_count", ctypes.c_uint64),
+                ("depth", ctypes.c_int32),
+                ("terminal_weight", ctypes.c_int32),
+                ("endgame_empties", ctypes.c_int32),
+                ("explore", ctypes.c_int32),
+                ("max_nodes", ctypes.c_uint64)]
+
+
+class OthNtupleTd(ctypes.Structure):
+    """struct oth_ntuple_td (include/othello_mi355x.h): host memory holding device
+    addresses, all required."""
+    _fields_ = [("boards", ctypes.c_void_p),
+                ("meta", ctypes.c_void_p),
+                ("targets", ctypes.c_void_p),
+                ("learn", ctypes.c_void_p)]
+
+
 # every symbol include/othello_mi355x.h declares: (restype, argtypes)
 _P = ctypes.c_void_p
 _I32, _U32, _U64, _I64 = ctypes.c_int32, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_int64
@@ -244,6 +270,10 @@ SIGNATURES = {
     "oth_play_cnet": (_I32, [_P, _P, _P, _I32, _P, _P, _P, _P]),
     "oth_reset_vs_cnet": (_I32, [_P, _P, _P, _P, _P]),
     "oth_step_vs_cnet": (_I32, [_P, _P, _P, _P, _P, _P, _P, _P]),
+    "oth_play_ntuple": (_I32, [_P, _P, _P, _I32, _P, _P, _P, _P, _P, _P]),
+    "oth_reset_vs_ntuple": (_I32, [_P, _P, _P, _P, _P]),
+    "oth_step_vs_ntuple": (_I32, [_P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "oth_ntuple_update_masked": (_I32, [_I32, _I32, _P, _P, _U64, _P, _U64, _P, _P, _P, _P, _I32, _I32, _P, _P]),
     "oth_reset_vs": (_I32, [_P, _I32, _P, _P, _P]),
     "oth_step_vs": (_I32, [_P, _I32, _P, _P, _P, _P, _P, _P]),
     "oth_step_vs_observe": (_I32, [_P, _I32, _P, _P, _P, _P, _P, _I32, _I32, _P, _P]),

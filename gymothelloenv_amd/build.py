@@ -11,7 +11,8 @@ csrc/play_cnet_n.hip (oth_play_cnet, oth_reset_vs_cnet, oth_step_vs_cnet: the co
 csrc/mcts_n.hip (oth_mcts) and csrc/puct_n.hip (oth_puct_begin, oth_puct_advance, oth_puct_result, oth_puct_pick,
 oth_puct_reroot) and csrc/replay_n.hip (oth_replay_begin, oth_replay_append, oth_replay_label, oth_replay_counts,
 oth_replay_gather, oth_replay_sample, oth_symmetry_masks) and csrc/ntuple_n.hip (oth_ntuple_eval,
-oth_ntuple_update, oth_search_ntuple: the n-tuple network) once per N,
+oth_ntuple_update, oth_search_ntuple: the n-tuple network) and csrc/play_ntuple_n.hip (oth_play_ntuple,
+oth_reset_vs_ntuple, oth_step_vs_ntuple: the n-tuple network as a player) once per N,
 csrc/net.hip (oth_net_eval: the int8 network on the matrix cores), csrc/cnet.hip (oth_cnet_eval: the int8
 residual convolutional network on the matrix cores) and csrc/noise.hip (oth_puct_noise: Dirichlet root noise in
 integers) once for every N,
@@ -41,7 +42,8 @@ SOURCES = ("capi.hip", "kernels_n.hip", "play_rand_n.hip", "masked.hip", "device
            "solve.hpp", "root_tasks.hpp", "search_n.hip", "search.hpp", "play_search_n.hip", "play_search.hpp",
            "mcts_n.hip", "mcts.hpp", "puct_n.hip", "puct.hpp", "replay_n.hip", "replay.hpp", "net.hip", "net.hpp",
            "noise.hip", "noise.hpp", "net_dev.hpp", "play_owner.hpp", "play_net_n.hip", "play_net.hpp", "cnet.hip",
-           "cnet.hpp", "cnet_dev.hpp", "play_cnet_n.hip", "play_cnet.hpp", "ntuple_n.hip", "ntuple.hpp")
+           "cnet.hpp", "cnet_dev.hpp", "play_cnet_n.hip", "play_cnet.hpp", "ntuple_n.hip", "ntuple.hpp",
+           "play_ntuple_n.hip", "play_ntuple.hpp")
 PLAY_SIZES = list(range(4, 12))  # k_play_rand (one-word boards) and k_play_rand_w (two-word boards)
 # play_rand_n.hip: the max-ILP machine scheduler (one wave per SIMD: latency hidden by the schedule
 # counts, occupancy does not); the rest of the library keeps the default scheduler
@@ -143,6 +145,8 @@ def build(force=False, verbose=True, extra_flags=(), out=OUT, jobs=None, only_si
               for n in SIZES]
     units += [(os.path.join(CSRC, "ntuple_n.hip"), os.path.join(objdir, "ntuple_n%d.o" % n), ["-DOTH_N=%d" % n])
               for n in SIZES]
+    units += [(os.path.join(CSRC, "play_ntuple_n.hip"), os.path.join(objdir, "play_ntuple_n%d.o" % n),
+               ["-DOTH_N=%d" % n]) for n in SIZES]
 
     def compile_one(u):
         src, obj, defs = u
@@ -164,7 +168,8 @@ def build(force=False, verbose=True, extra_flags=(), out=OUT, jobs=None, only_si
             "playouts_n%d.o" % n for n in only_sizes} | {"solve_n%d.o" % n for n in only_sizes} | {
             "search_n%d.o" % n for n in only_sizes} | {"play_search_n%d.o" % n for n in only_sizes} | {"play_net_n%d.o" % n for n in only_sizes} | {"play_cnet_n%d.o" % n for n in only_sizes} | {
             "mcts_n%d.o" % n for n in only_sizes} | {"puct_n%d.o" % n for n in only_sizes} | {
-            "replay_n%d.o" % n for n in only_sizes} | {"ntuple_n%d.o" % n for n in only_sizes}
+            "replay_n%d.o" % n for n in only_sizes} | {"ntuple_n%d.o" % n for n in only_sizes} | {
+            "play_ntuple_n%d.o" % n for n in only_sizes}
     if only_sizes is not None or only_units is not None:
         reuse = [os.path.join(OBJDIR, os.path.basename(u[1])) for u in units if os.path.basename(u[1]) not in keep]
         units = [u for u in units if os.path.basename(u[1]) in keep]

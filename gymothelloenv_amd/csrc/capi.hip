@@ -956,6 +956,14 @@ int oth_ntuple_update(int32_t board_size, int32_t n_rows, const oth_ntuple_param
                       uint64_t plan_bytes, int32_t* weights, uint64_t weight_count, const uint64_t* boards,
                       const uint16_t* meta, const int32_t* targets, int32_t rate, int32_t rate_shift, int32_t* deltas,
                       oth_stream_t stream) {
+    return oth_ntuple_update_masked(board_size, n_rows, params, plan, plan_bytes, weights, weight_count, boards, meta,
+                                    targets, nullptr, rate, rate_shift, deltas, stream);
+}
+
+int oth_ntuple_update_masked(int32_t board_size, int32_t n_rows, const oth_ntuple_params* params, const void* plan,
+                             uint64_t plan_bytes, int32_t* weights, uint64_t weight_count, const uint64_t* boards,
+                             const uint16_t* meta, const int32_t* targets, const uint8_t* mask, int32_t rate,
+                             int32_t rate_shift, int32_t* deltas, oth_stream_t stream) {
     if (!boards || !meta) return fail(OTH_EINVAL, "boards or meta is NULL");
     if (!targets) return fail(OTH_EINVAL, "targets is NULL");
     if (!deltas) return fail(OTH_EINVAL, "deltas is NULL");
@@ -968,7 +976,7 @@ int oth_ntuple_update(int32_t board_size, int32_t n_rows, const oth_ntuple_param
     if (n_rows == 0) return OTH_OK;
     const NtupleKey key = ntuple_key(board_size, np);
     return with_n(board_size, [&](auto NC) {
-        return launch_ntuple_update<decltype(NC)::value>(n_rows, plan, key, weights, boards, meta, targets, rate,
+        return launch_ntuple_update<decltype(NC)::value>(n_rows, plan, key, weights, boards, meta, targets, mask, rate,
                                                          rate_shift, deltas, (hipStream_t)stream);
     });
 }
@@ -1248,6 +1256,89 @@ int oth_step_vs_cnet(oth_env* env, const oth_cnet_policy* opponent, const int32_
         return launch_play_cnet<decltype(NC)::value>(env, OTH_PLAY_SEARCH_STEP_VS, opponent, opponent, 0, actions,
                                                      protagonist, nullptr, nullptr, rewards, dones, plies, call,
                                                      (hipStream_t)stream);
+    });
+}
+
+}  // extern "C"
+
+namespace {
+// an oth_ntuple_policy against the handle's board size: the parameters, the device arguments, the search's ranges
+// and the exploration's; who: the argument's name for the message; *key: what the plan's header must hold
+int check_ntuple_policy(const oth_env* env, const oth_ntuple_policy* p, const char* who, NtupleKey* key) {
+    char msg[200];
+    if (!p) {
+        snprintf(msg, sizeof(msg), "n-tuple policy `%s` is NULL", who);
+        return fail(OTH_EINVAL, msg);
+    }
+    NtupleParams np;
+    if (int rc = ntuple_params(env->n, &p->params, &np)) return rc;
+    if (int rc = ntuple_device_args(np, p->plan, p->plan_bytes, p->weights, p->weight_count)) return rc;
+    const char* why = nullptr;
+    if (p->depth < 1 || p->depth > OTH_SEARCH_MAX_DEPTH) why = "depth must be in [1, 14]";
+    else if (p->terminal_weight < 1 || p->terminal_weight > 32767) why = "terminal_weight must be in [1, 32767]";
+    else if (p->endgame_empties < 0 || p->endgame_empties > OTH_SEARCH_MAX_DEPTH)
+        why = "endgame_empties must be in [0, 14]";
+    else if (p->explore < 0 || p->explore > OTH_NTUPLE_EXPLORE_ONE) why = "explore must be in [0, 65536]";
+    else if (p->max_nodes < 1 || p->max_nodes > 0xffffffffull) why = "max_nodes must be in [1, 2^32 - 1]";
+    if (why) {
+        snprintf(msg, sizeof(msg), "n-tuple policy `%s`: %s", who, why);
+        return fail(OTH_EINVAL, msg);
+    }
+    *key = ntuple_key(env->n, np);
+    return OTH_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int oth_play_ntuple(oth_env* env, const oth_ntuple_policy* black, const oth_ntuple_policy* white, int32_t n_plies,
+                    int32_t* actions, int32_t* rewards, uint8_t* dones, uint8_t* fallbacks, const oth_ntuple_td* td,
+                    oth_stream_t stream) {
+    // the argument checks come before the handle's device is touched
+    if (!env) return fail(OTH_EINVAL, "NULL oth_env");
+    NtupleKey kb, kw;
+    if (int rc = check_ntuple_policy(env, black, "black", &kb)) return rc;
+    if (int rc = check_ntuple_policy(env, white, "white", &kw)) return rc;
+    if (n_plies < 1) return fail(OTH_EINVAL, "n_plies must be >= 1");
+    if (td && (!td->boards || !td->meta || !td->targets || !td->learn))
+        return fail(OTH_EINVAL, "a member of td is NULL");
+    if (int rc = use_device(env)) return rc;
+    const uint64_t ply0 = env->ply;
+    env->ply += (uint64_t)n_plies;
+    return with_n(env->n, [&](auto NC) {
+        return launch_play_ntuple<decltype(NC)::value>(env, OTH_PLAY_SEARCH_PLAY, black, kb, white, kw, n_plies,
+                                                       nullptr, nullptr, nullptr, actions, rewards, dones, fallbacks,
+                                                       nullptr, nullptr, td, ply0, (hipStream_t)stream);
+    });
+}
+
+int oth_reset_vs_ntuple(oth_env* env, const oth_ntuple_policy* opponent, const int8_t* protagonist,
+                        const uint8_t* mask, oth_stream_t stream) {
+    if (!env) return fail(OTH_EINVAL, "NULL oth_env");
+    NtupleKey key;
+    if (int rc = check_ntuple_policy(env, opponent, "opponent", &key)) return rc;
+    if (int rc = use_device(env)) return rc;
+    const uint64_t call = env->ply++;
+    return with_n(env->n, [&](auto NC) {
+        return launch_play_ntuple<decltype(NC)::value>(env, OTH_PLAY_SEARCH_RESET_VS, opponent, key, opponent, key, 0,
+                                                       nullptr, protagonist, mask, nullptr, nullptr, nullptr, nullptr,
+                                                       nullptr, nullptr, nullptr, call, (hipStream_t)stream);
+    });
+}
+
+int oth_step_vs_ntuple(oth_env* env, const oth_ntuple_policy* opponent, const int32_t* actions,
+                       const int8_t* protagonist, int32_t* rewards, uint8_t* dones, int32_t* plies,
+                       int32_t* fallbacks, oth_stream_t stream) {
+    if (!env) return fail(OTH_EINVAL, "NULL oth_env");
+    NtupleKey key;
+    if (int rc = check_ntuple_policy(env, opponent, "opponent", &key)) return rc;
+    if (!actions) return fail(OTH_EINVAL, "actions is NULL");
+    if (int rc = use_device(env)) return rc;
+    const uint64_t call = env->ply++;
+    return with_n(env->n, [&](auto NC) {
+        return launch_play_ntuple<decltype(NC)::value>(env, OTH_PLAY_SEARCH_STEP_VS, opponent, key, opponent, key, 0,
+                                                       actions, protagonist, nullptr, nullptr, rewards, dones, nullptr,
+                                                       plies, fallbacks, nullptr, call, (hipStream_t)stream);
     });
 }
 

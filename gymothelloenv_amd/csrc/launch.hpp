@@ -254,17 +254,28 @@ int launch_puct_noise(oth_env* env, int rows_per_board, const uint8_t* kind, con
 
 // k_ntuple_eval (oth_ntuple_eval), k_ntuple_delta + k_ntuple_add (oth_ntuple_update) and k_search_ntuple
 // (oth_search_ntuple) in ntuple_n.hip, every N, a unit of its own per board size.  The arguments are checked,
-// n_rows >= 1; key: what the plan's header must hold (ntuple.hpp).
+// n_rows >= 1; key: what the plan's header must hold (ntuple.hpp).  mask (oth_ntuple_update_masked): NULL, or
+// the rows that learn.
 template <int N>
 int launch_ntuple_eval(int n_rows, const void* plan, const oth::NtupleKey& key, const int32_t* weights,
                        const uint64_t* boards, const uint16_t* meta, int32_t* values, int64_t* sums, hipStream_t st);
 template <int N>
 int launch_ntuple_update(int n_rows, const void* plan, const oth::NtupleKey& key, int32_t* weights,
-                         const uint64_t* boards, const uint16_t* meta, const int32_t* targets, int32_t rate,
-                         int rate_shift, int32_t* deltas, hipStream_t st);
+                         const uint64_t* boards, const uint16_t* meta, const int32_t* targets, const uint8_t* mask,
+                         int32_t rate, int rate_shift, int32_t* deltas, hipStream_t st);
 template <int N>
 int launch_search_ntuple(oth_env* env, int depth, const void* plan, const oth::NtupleKey& key, const int32_t* weights,
                          int terminal, uint32_t max_nodes, int32_t* value, int32_t* best, int32_t* move_values,
                          uint8_t* status, uint64_t* nodes, hipStream_t st);
+
+// k_play_ntuple (oth_play_ntuple, oth_reset_vs_ntuple, oth_step_vs_ntuple) in play_ntuple_n.hip, every N, a unit
+// of its own per board size: launch_play_search's arguments with n-tuple policies, the keys their plans' headers
+// must hold, and td (play mode only; NULL: no rows).  The arguments are checked.
+template <int N>
+int launch_play_ntuple(oth_env* env, int mode, const oth_ntuple_policy* black, const oth::NtupleKey& key_b,
+                       const oth_ntuple_policy* white, const oth::NtupleKey& key_w, int n_plies, const int32_t* act_in,
+                       const int8_t* prot, const uint8_t* mask, int32_t* actions, int32_t* rewards, uint8_t* dones,
+                       uint8_t* fb_ply, int32_t* plies, int32_t* fb_cnt, const oth_ntuple_td* td, uint64_t ctr,
+                       hipStream_t st);
 
 }  // namespace oth_host

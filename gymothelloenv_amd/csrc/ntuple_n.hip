@@ -1,5 +1,5 @@
-// ntuple_n.hip -- k_ntuple_eval (oth_ntuple_eval), k_ntuple_delta and k_ntuple_add (oth_ntuple_update's two
-// launches) and k_search_ntuple (oth_search_ntuple): the n-tuple network of ntuple.hpp in a translation unit of
+// ntuple_n.hip -- k_ntuple_eval (oth_ntuple_eval), k_ntuple_delta and k_ntuple_add (oth_ntuple_update's and
+// oth_ntuple_update_masked's two launches) and k_search_ntuple (oth_search_ntuple): the n-tuple network of ntuple.hpp in a translation unit of
 // its own per board size (-DOTH_N=4 .. 16), like search_n.hip.
 //
 // Rows (eval, delta, add): a group of NTUPLE_LANES = 8 lanes a row, lane s of the group taking symmetry s.  The
@@ -76,14 +76,17 @@ __global__ __launch_bounds__(NTUPLE_BLOCK) void k_ntuple_delta(int R, const uint
                                                                const int32_t* __restrict__ w,
                                                                const uint64_t* __restrict__ boards,
                                                                const uint16_t* __restrict__ meta,
-                                                               const int32_t* __restrict__ targets, int32_t rate,
+                                                               const int32_t* __restrict__ targets,
+                                                               const uint8_t* __restrict__ mask, int32_t rate,
                                                                int rate_shift, int32_t* __restrict__ deltas) {
     __shared__ uint32_t g_plan[NTUPLE_PLAN_WORDS];
     if (!plan_to_lds(plan, key, g_plan)) return;
     const long long r = (long long)blockIdx.x * NTUPLE_ROWS + threadIdx.x / NTUPLE_LANES;
     const int s = threadIdx.x % NTUPLE_LANES;
     const int64_t S = group_sum<Geo<N>::W>(g_plan, key, w, boards, meta, (size_t)(r < R ? r : R - 1), s);
-    if (r < R && s == 0) deltas[r] = ntuple_delta(targets[r], ntuple_value(S, (int)key.shift), rate, rate_shift);
+    // (a row the mask leaves out: d = 0, which k_ntuple_add skips)
+    if (r < R && s == 0)
+        deltas[r] = mask && !mask[r] ? 0 : ntuple_delta(targets[r], ntuple_value(S, (int)key.shift), rate, rate_shift);
 }
 
 template <int N>
@@ -147,11 +150,11 @@ int launch_ntuple_eval(int n_rows, const void* plan, const NtupleKey& key, const
 
 template <int N>
 int launch_ntuple_update(int n_rows, const void* plan, const NtupleKey& key, int32_t* weights, const uint64_t* boards,
-                         const uint16_t* meta, const int32_t* targets, int32_t rate, int rate_shift, int32_t* deltas,
-                         hipStream_t st) {
+                         const uint16_t* meta, const int32_t* targets, const uint8_t* mask, int32_t rate, int rate_shift,
+                         int32_t* deltas, hipStream_t st) {
     const dim3 grid((unsigned)(((long long)n_rows + NTUPLE_ROWS - 1) / NTUPLE_ROWS)), block(NTUPLE_BLOCK);
     launch_k(k_ntuple_delta<N>, grid, block, 0, st, n_rows, static_cast<const uint32_t*>(plan), key,
-             static_cast<const int32_t*>(weights), boards, meta, targets, rate, rate_shift, deltas);
+             static_cast<const int32_t*>(weights), boards, meta, targets, mask, rate, rate_shift, deltas);
     launch_k(k_ntuple_add<N>, grid, block, 0, st, n_rows, static_cast<const uint32_t*>(plan), key,
              reinterpret_cast<uint32_t*>(weights), boards, meta, static_cast<const int32_t*>(deltas));
     return after_launch("oth_ntuple_update");
@@ -171,7 +174,7 @@ int launch_search_ntuple(oth_env* env, int depth, const void* plan, const Ntuple
 template int launch_ntuple_eval<OTH_N>(int, const void*, const NtupleKey&, const int32_t*, const uint64_t*,
                                        const uint16_t*, int32_t*, int64_t*, hipStream_t);
 template int launch_ntuple_update<OTH_N>(int, const void*, const NtupleKey&, int32_t*, const uint64_t*, const uint16_t*,
-                                         const int32_t*, int32_t, int, int32_t*, hipStream_t);
+                                         const int32_t*, const uint8_t*, int32_t, int, int32_t*, hipStream_t);
 template int launch_search_ntuple<OTH_N>(oth_env*, int, const void*, const NtupleKey&, const int32_t*, int, uint32_t,
                                          int32_t*, int32_t*, int32_t*, uint8_t*, uint64_t*, hipStream_t);
 

@@ -38,6 +38,7 @@ constexpr uint32_t RNG_PUCT_PICK = 4;  // oth_puct_pick's sampled move (3 is the
 constexpr uint32_t RNG_REPLAY_SAMPLE = 5;  // oth_replay_sample's row and symmetry (replay.hpp)
 constexpr uint32_t RNG_PUCT_NOISE = 6;  // oth_puct_noise's table draws (noise.hpp); bits 8 .. 15 hold the block of squares
 constexpr uint32_t RNG_NET_MOVE = 7;  // the network's sampled move (play_net.hpp: oth_play_net and the vs calls)
+constexpr uint32_t RNG_NTUPLE_EXPLORE = 8;  // the n-tuple player's exploring ply (play_ntuple.hpp: oth_play_ntuple and the vs calls)
 
 template <int N>
 struct Start {  // _reset_board (othello.py:256-263): W at (c-1,c-1),(c,c); B at (c,c-1),(c-1,c)

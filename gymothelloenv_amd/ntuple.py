@@ -8,9 +8,14 @@ sets of squares, applied under the eight board symmetries.
                        delta-rule step, exact and order-independent) and rate_for
     snake_tuples       random connected walks, the usual choice of tuples
     ntuple_evaluator   the net as an evaluator of VecOthelloEnv.puct_search
+    NTuplePlayer       the net as a player (oth_play_ntuple, oth_reset_vs_ntuple,
+                       oth_step_vs_ntuple): VecOthelloEnv.play_ntuple, an opponent of
+                       reset_vs / step_vs, and with NTupleNet.td_play a TD(0) round in
+                       two calls (TDRows: the rows the play launch recorded)
 
 VecOthelloEnv.search_ntuple / search_ntuple_actions look ahead over the net, and
 policies.NTuplePolicy plays it in the drop-in OthelloEnv."""
+import collections
 import ctypes
 
 import numpy as np
@@ -93,6 +98,7 @@ class NTupleNet(object):
         for t in self.tuples[:-1]:
             self.offsets.append(self.offsets[-1] + 3 ** len(t))
         self.weights = torch.zeros(self.weight_count, dtype=torch.int32, device=self.device)
+        self._td_players = {}  # (depth, explore) -> td_play's NTuplePlayer
 
     def _rows(self, boards, meta):
         W = (self.board_size * self.board_size + 63) // 64
@@ -126,26 +132,59 @@ class NTupleNet(object):
                                               _ptr(values), _ptr(sm), _stream(self.device)), "oth_ntuple_eval")
         return (values, sm) if sums else values
 
-    def update(self, boards, meta, targets, rate, rate_shift):
+    def update(self, boards, meta, targets, rate, rate_shift, mask=None):
         """One delta-rule step on the rows, in place on `weights`: with v the value of a
         row under the weights before the call, d = clamp(round((clamp(target, -32768,
         32768) - v) rate / 2^rate_shift), -2^30, 2^30) is added to every entry the row
         hits, once per hit, and to the bias.  Integer additions: the result is the same
-        whatever the order.  Returns the deltas, int32 (R,)."""
+        whatever the order.  mask (oth_ntuple_update_masked): a uint8 / bool tensor
+        (R,), a row it leaves out gets delta 0 and adds nothing -- the rows stay where
+        they are and nothing is read back to count them.  Returns the deltas, int32 (R,)."""
         R, bd, mt = self._rows(boards, meta)
         w = self._weights()
         tg = targets.to(device=self.device, dtype=torch.int32).contiguous()
         if tg.numel() != R:
             raise ValueError("expected %d targets, got %d" % (R, tg.numel()))
+        mk = None
+        if mask is not None:
+            mk = mask.to(device=self.device).contiguous()
+            mk = mk.view(torch.uint8) if mk.dtype == torch.bool else mk.to(torch.uint8)
+            if mk.numel() != R:
+                raise ValueError("expected a mask of %d rows, got %d" % (R, mk.numel()))
         deltas = torch.empty(R, dtype=torch.int32, device=self.device)
         if R == 0:
             return deltas
         with torch.cuda.device(self.device):
-            L.check(self._lib.oth_ntuple_update(self.board_size, R, ctypes.byref(self.params), _ptr(self.plan),
-                                                self.plan_bytes, _ptr(w), self.weight_count, _ptr(bd), _ptr(mt),
-                                                _ptr(tg), int(rate), int(rate_shift), _ptr(deltas),
-                                                _stream(self.device)), "oth_ntuple_update")
+            if mk is None:
+                L.check(self._lib.oth_ntuple_update(self.board_size, R, ctypes.byref(self.params), _ptr(self.plan),
+                                                    self.plan_bytes, _ptr(w), self.weight_count, _ptr(bd), _ptr(mt),
+                                                    _ptr(tg), int(rate), int(rate_shift), _ptr(deltas),
+                                                    _stream(self.device)), "oth_ntuple_update")
+            else:
+                L.check(self._lib.oth_ntuple_update_masked(self.board_size, R, ctypes.byref(self.params),
+                                                           _ptr(self.plan), self.plan_bytes, _ptr(w),
+                                                           self.weight_count, _ptr(bd), _ptr(mt), _ptr(tg), _ptr(mk),
+                                                           int(rate), int(rate_shift), _ptr(deltas),
+                                                           _stream(self.device)), "oth_ntuple_update_masked")
         return deltas
+
+    def td_play(self, env, n_plies, rate, rate_shift, explore=0.0, depth=1):
+        """One TD(0) round in two calls and no host synchronisation: n_plies plies of
+        self-play under this net on both sides (VecOthelloEnv.play_ntuple with td=True:
+        an NTuplePlayer of `depth` that explores with probability `explore`), then one
+        masked update over the n_plies * E rows with the rows' `learn` as the mask.
+        The weights are frozen during the play launch: batch semantics, exact and
+        order-independent.  Returns play_ntuple's result, the TDRows last."""
+        key = (int(depth), float(explore))
+        player = self._td_players.get(key)
+        if player is None:
+            player = self._td_players[key] = NTuplePlayer(self, depth=depth, explore=explore)
+        res = env.play_ntuple(player, None, n_plies, td=True)
+        rows = res[-1]
+        R = rows.learn.numel()
+        self.update(rows.boards.view(R, -1), rows.meta.view(R), rows.targets.view(R), rate, rate_shift,
+                    mask=rows.learn.view(R))
+        return res
 
     def rate_for(self, alpha, rows):
         """(rate, rate_shift) of a step `alpha` in value space for a batch of `rows`
@@ -173,6 +212,63 @@ class NTupleNet(object):
     def __repr__(self):
         return "NTupleNet(<%d x %d, %d tuples, %d weights>, value_shift=%d)" % (
             self.board_size, self.board_size, len(self.tuples), self.weight_count, self.value_shift)
+
+
+TDRows = collections.namedtuple("TDRows", "boards meta targets learn")
+TDRows.__doc__ = """The TD(0) rows of VecOthelloEnv.play_ntuple(td=True) (struct oth_ntuple_td): boards int64
+(n_plies, E, 2W) and meta int16 (n_plies, E), the row before each ply; targets int32 (n_plies, E), from
+that row's mover's side; learn uint8 (n_plies, E), 1 where the ply was a finished search's move of a live
+board -- every other row is zero."""
+
+
+class NTuplePlayer(object):
+    """An n-tuple network as a player (struct oth_ntuple_policy): the move of a board with
+    e empty squares is oth_search_ntuple's `best` over `net` at depth e when e <=
+    endgame_empties, else at `depth`; where the search runs over max_nodes (per root
+    move) GreedyPolicy moves and the ply counts as a fallback.  Before the search, with
+    probability `explore` (stored as round(65536 explore), a draw keyed by the env's
+    seed, the board's global id and the ply) the ply explores: a uniform move of the
+    stored possible moves, no fallback, no TD row.  Used by VecOthelloEnv.play_ntuple
+    and as `opponent` of reset_vs / step_vs.  The net's weights are read as they are
+    when a launch runs."""
+
+    kind = "ntuple"
+
+    def __init__(self, net, depth=1, endgame_empties=0, explore=0.0, terminal=64, max_nodes=1 << 22):
+        if not isinstance(net, NTupleNet):
+            raise TypeError("NTuplePlayer takes an NTupleNet")
+        for name, v, lo, hi in (("depth", depth, 1, L.OTH_SEARCH_MAX_DEPTH), ("terminal", terminal, 1, 32767),
+                                ("endgame_empties", endgame_empties, 0, L.OTH_SEARCH_MAX_DEPTH),
+                                ("max_nodes", max_nodes, 1, 2 ** 32 - 1)):
+            if isinstance(v, bool) or int(v) != v:
+                raise ValueError("%s must be an integer" % name)
+            if not lo <= int(v) <= hi:
+                raise ValueError("%s must be in [%d, %d]" % (name, lo, hi))
+        if not 0.0 <= float(explore) <= 1.0:
+            raise ValueError("explore must be in [0, 1]")
+        self.net = net
+        self.depth, self.terminal = int(depth), int(terminal)
+        self.endgame_empties, self.max_nodes = int(endgame_empties), int(max_nodes)
+        self.explore = int(round(L.OTH_NTUPLE_EXPLORE_ONE * float(explore)))
+        self._pol = None
+
+    def _policy(self, env):
+        """The struct for a call on env, with the net's weights as they are now (kept alive here)."""
+        net = self.net
+        net._check_env(env)
+        w = net._weights()
+        pol = L.OthNtuplePolicy()
+        ctypes.memmove(ctypes.byref(pol.params), ctypes.byref(net.params), ctypes.sizeof(L.OthNtupleParams))
+        pol.plan, pol.plan_bytes = net.plan.data_ptr(), net.plan_bytes
+        pol.weights, pol.weight_count = w.data_ptr(), net.weight_count
+        pol.depth, pol.terminal_weight, pol.endgame_empties = self.depth, self.terminal, self.endgame_empties
+        pol.explore, pol.max_nodes = self.explore, self.max_nodes
+        self._pol = (pol, w)
+        return pol
+
+    def __repr__(self):
+        return "NTuplePlayer(%r, depth=%d, endgame_empties=%d, explore=%d/65536, terminal=%d, max_nodes=%d)" % (
+            self.net, self.depth, self.endgame_empties, self.explore, self.terminal, self.max_nodes)
 
 
 class ntuple_evaluator(object):

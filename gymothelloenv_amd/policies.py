@@ -16,6 +16,7 @@ import numpy as np
 from . import _lib as L
 from .othello import WHITE_DISK
 from .vec_env import SearchConfig  # noqa: F401  (SearchPolicy's batched counterpart: the search played on the device)
+from .ntuple import NTuplePlayer  # noqa: F401  (NTuplePolicy's batched counterpart: the n-tuple net played on the device)
 
 PROTAGONIST_TURN = 1  # simple_policies.py:8-9
 OPPONENT_TURN = -1
@@ -311,20 +312,49 @@ class NTuplePolicy(object):
     learned counterpart of SearchPolicy): the move is oth_search_ntuple's `best` at
     `depth` over `net` (an ntuple.NTupleNet), a game end valued by `terminal`.  Where
     the search runs over its node budget (ABORTED) GreedyPolicy moves, as for
-    SearchPolicy."""
+    SearchPolicy.
 
-    def __init__(self, net, depth=1, terminal=64):
+    `net` may be an ntuple.NTuplePlayer instead: the move is then
+    VecOthelloEnv.play_ntuple's for the board, computed by the same kernel -- the
+    player's depth, endgame_empties, budget and exploring draws -- on a one-board
+    scratch env that plays one ply of it, as NetPolicy does; seed(seed) keys the
+    scratch env's draws."""
+
+    def __init__(self, net, depth=1, terminal=64, seed=0):
         self.env = None
-        self.net, self.depth, self.terminal = net, int(depth), int(terminal)
+        self.player = net if getattr(net, "kind", None) == "ntuple" else None
+        self.net = net.net if self.player is not None else net
+        self.depth, self.terminal = int(depth), int(terminal)
         self.fallback = GreedyPolicy()
+        self._seed = int(seed)
+        self._scratch = None
 
     def reset(self, env):
         self.env = _base(env)
         self.fallback.reset(env)
 
+    def seed(self, seed):
+        if seed is not None and int(seed) != self._seed:
+            self._seed = int(seed)
+            self._scratch = None
+
+    def _player_action(self):
+        from .vec_env import VecOthelloEnv
+        vec = self.env._vec
+        if self._scratch is None or self._scratch.board_size != vec.board_size:
+            self._scratch = VecOthelloEnv(1, board_size=vec.board_size, sudden_death_on_invalid_move=False,
+                                          seed=self._seed, device=vec.device)
+        self._scratch.set_state(*vec.get_state())
+        a = int(self._scratch.play_ntuple(self.player, n_plies=1)[0].cpu()[0, 0])
+        if a < 0:
+            raise ValueError('no possible moves')
+        return a
+
     def get_action(self, obs):
         vec = self.env._vec
         self.env._sync()
+        if self.player is not None:
+            return self._player_action()
         best, status = vec.search_ntuple(self.depth, self.net, terminal=self.terminal, best=True, status=True)[1:]
         if int(status.cpu()[0]) == L.OTH_SEARCH_DONE:
             return int(best.cpu()[0])

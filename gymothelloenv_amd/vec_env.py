@@ -399,6 +399,44 @@ class VecOthelloEnv(object):
                      self._stream()), what)
         return a, r, d
 
+    def play_ntuple(self, black, white=None, n_plies=1, record=True, fallbacks=False, td=False):
+        """n_plies plies where every board's mover plays its colour's n-tuple player's
+        move (oth_play_ntuple): play_search with the move replaced by the
+        NTuplePlayer's -- `black` for black's plies, `white` (None: `black`) for
+        white's; the two may differ in everything -- in one launch that never
+        synchronises the host: an exploring ply's uniform move, else the alpha-beta's
+        best move over the net, GreedyPolicy's where the search ran over max_nodes.
+        Random-opening plies, terminated boards, auto-reset, the tallies and the ply
+        counter are step_policy's.
+
+        Returns play_search's result -- (actions, rewards, dones) of shape (n_plies, E)
+        (None if not recorded), with fallbacks=True a uint8 (n_plies, E) tensor -- and
+        with td=True an ntuple.TDRows last: the TD(0) rows of the plies from the same
+        launch, what NTupleNet.update takes with `learn` as its mask."""
+        from .ntuple import NTuplePlayer, TDRows
+        if not isinstance(black, NTuplePlayer) or not (white is None or isinstance(white, NTuplePlayer)):
+            raise TypeError("play_ntuple takes NTuplePlayer objects")
+        n_plies = int(n_plies)
+        if n_plies < 1:
+            raise ValueError("n_plies must be >= 1")
+        pb = black._policy(self)
+        pw = pb if white is None or white is black else white._policy(self)
+        E = self.num_envs
+        a = r = d = None
+        if record:
+            a, r, d = self._i32(n_plies, E), self._i32(n_plies, E), self._u8(n_plies, E)
+        f = self._u8(n_plies, E) if fallbacks else None
+        rows = tdp = None
+        if td:
+            rows = TDRows(torch.empty(n_plies, E, 2 * self.words, dtype=torch.int64, device=self.device),
+                          torch.empty(n_plies, E, dtype=torch.int16, device=self.device), self._i32(n_plies, E),
+                          self._u8(n_plies, E))
+            tds = L.OthNtupleTd(*[t.data_ptr() for t in rows])
+            tdp = ctypes.addressof(tds)
+        L.check(self._lib.oth_play_ntuple(self._h, ctypes.addressof(pb), ctypes.addressof(pw), n_plies, _ptr(a),
+                                          _ptr(r), _ptr(d), _ptr(f), tdp, self._stream()), "oth_play_ntuple")
+        return (a, r, d) + ((f,) if fallbacks else ()) + ((rows,) if td else ())
+
     # ------------------------------------------- OthelloEnv semantics on device
     def _protagonist(self, protagonist):
         if protagonist is None:
@@ -418,7 +456,8 @@ class VecOthelloEnv(object):
         black; int or per-board tensor) is to move.  `opponent` may be a
         SearchConfig: the opponent then plays its searched move (oth_reset_vs_search);
         or a NetPlayer: it plays its network's move (oth_reset_vs_net, or
-        oth_reset_vs_cnet for a conv net)."""
+        oth_reset_vs_cnet for a conv net); or an NTuplePlayer: its n-tuple player's
+        move (oth_reset_vs_ntuple)."""
         from .net import NetPlayer
         prot = self._protagonist(protagonist)
         m = None if mask is None else mask.to(device=self.device, dtype=torch.uint8).contiguous()
@@ -430,6 +469,10 @@ class VecOthelloEnv(object):
         if isinstance(opponent, SearchConfig):
             L.check(self._lib.oth_reset_vs_search(self._h, ctypes.addressof(opponent._policy(self)), _ptr(prot),
                                                   _ptr(m), self._stream()), "oth_reset_vs_search")
+            return self.get_observation()
+        if getattr(opponent, "kind", None) == "ntuple":  # an ntuple.NTuplePlayer
+            L.check(self._lib.oth_reset_vs_ntuple(self._h, ctypes.addressof(opponent._policy(self)), _ptr(prot),
+                                                  _ptr(m), self._stream()), "oth_reset_vs_ntuple")
             return self.get_observation()
         L.check(self._lib.oth_reset_vs(self._h, _POLICIES[opponent], _ptr(prot), _ptr(m), self._stream()),
                 "oth_reset_vs")
@@ -449,6 +492,8 @@ class VecOthelloEnv(object):
         observation comes from an observe launch after it, and with fallbacks=True
         a fifth result counts, per board, the opponent's plies of this call whose
         search ran over max_nodes and were played by GreedyPolicy (int32 (E,)).
+        An NTuplePlayer opponent (oth_step_vs_ntuple) goes the same way, fallbacks
+        included.
 
         `opponent` may be a NetPlayer: the opponent plays its network's move
         (oth_step_vs_net, or oth_step_vs_cnet for a conv net: one launch, no host
@@ -473,14 +518,16 @@ class VecOthelloEnv(object):
             if observe:
                 L.check(self._lib.oth_observe(self._h, lay, _DTYPES[o.dtype], _ptr(o), self._stream()), "oth_observe")
             return o, r, d.view(torch.bool), n
-        if isinstance(opponent, SearchConfig):
+        ntuple = getattr(opponent, "kind", None) == "ntuple"  # an ntuple.NTuplePlayer
+        if isinstance(opponent, SearchConfig) or ntuple:
             f = self._i32(self.num_envs) if fallbacks else None
             o = None
             if observe:
                 lay, o = self._obs_out(obs_layout, obs_dtype, obs)
-            L.check(self._lib.oth_step_vs_search(self._h, ctypes.addressof(opponent._policy(self)), _ptr(a),
-                                                 _ptr(prot), _ptr(r), _ptr(d), _ptr(n), _ptr(f), self._stream()),
-                    "oth_step_vs_search")
+            call, what = ((self._lib.oth_step_vs_ntuple, "oth_step_vs_ntuple") if ntuple else
+                          (self._lib.oth_step_vs_search, "oth_step_vs_search"))
+            L.check(call(self._h, ctypes.addressof(opponent._policy(self)), _ptr(a), _ptr(prot), _ptr(r), _ptr(d),
+                         _ptr(n), _ptr(f), self._stream()), what)
             if observe:
                 L.check(self._lib.oth_observe(self._h, lay, _DTYPES[o.dtype], _ptr(o), self._stream()), "oth_observe")
             res = (o, r, d.view(torch.bool), n)

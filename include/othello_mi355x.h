@@ -1436,6 +1436,105 @@ int oth_reset_vs_cnet(oth_env *env, const oth_cnet_policy *opponent, const int8_
 int oth_step_vs_cnet(oth_env *env, const oth_cnet_policy *opponent, const int32_t *actions, const int8_t *protagonist,
                      int32_t *rewards, uint8_t *dones, int32_t *plies, oth_stream_t stream);
 
+/* The n-tuple network as a player: one colour's (or the embedded opponent's)
+ * move chooser is oth_search_ntuple's computation over an oth_ntuple network.
+ * The struct is host memory, read during the call, as oth_search_policy is.
+ *
+ * The move T(board, p) is oth_search_policy's S, word for word, with
+ * oth_search_ntuple's computation in place of oth_search's: with e the board's
+ * number of empty squares, d = e if e <= p.endgame_empties, else d = p.depth;
+ * the search runs on the board with depth d, p's params, plan, weights,
+ * terminal_weight and max_nodes (per root move); the root list is the board's
+ * stored possible_moves.  Status DONE: T is `best`.  Status ABORTED: T is
+ * oth_greedy_actions' move and the ply counts as a fallback.
+ *
+ * Exploration comes before the search.  x = the Philox4x32-10 block with key
+ * `seed` and counter words (id, g lo, g hi, 8) -- purpose 8, a purpose of its own
+ * -- with id the global env id (env_id_base + e mod 2^32) and g the ply's global
+ * index, exactly as oth_play_net defines it: ply counter + p in oth_play_ntuple,
+ * c*256 + j in the vs calls.  The ply explores iff (x word 0 >> 16) < p.explore:
+ * the move is then the k-th square of the stored mask in ascending order (from
+ * 0), k = floor(x word 1 * count / 2^32) with count the mask's squares, and the
+ * ply is no fallback.  explore = 0 never draws, explore = OTH_NTUPLE_EXPLORE_ONE
+ * always explores; epsilon = explore / 65536.  The draw depends on the seed, the
+ * global id and the ply alone: a sharded run equals the unsharded one. */
+#define OTH_NTUPLE_EXPLORE_ONE 65536
+typedef struct oth_ntuple_policy {
+    oth_ntuple_params params;   /* as oth_ntuple_eval takes them */
+    const void *plan;           /* DEVICE: oth_ntuple_plan's bytes, 8-byte aligned */
+    uint64_t plan_bytes;        /* at least what oth_ntuple_plan_bytes reports */
+    const int32_t *weights;     /* DEVICE int32[n_weights + 1] */
+    uint64_t weight_count;      /* at least what oth_ntuple_weight_count reports */
+    int32_t depth;              /* [1, OTH_SEARCH_MAX_DEPTH] */
+    int32_t terminal_weight;    /* [1, 32767] */
+    int32_t endgame_empties;    /* [0, OTH_SEARCH_MAX_DEPTH] */
+    int32_t explore;            /* [0, 65536]: epsilon in 1/65536 */
+    uint64_t max_nodes;         /* [1, 2^32 - 1], per root move */
+} oth_ntuple_policy;
+
+/* The TD(0) rows of oth_play_ntuple's plies, from the same launch: host memory
+ * holding DEVICE addresses, all four required.  For ply p of board e, learn is 1
+ * iff the board was live before the ply, had a non-empty stored mask, the ply
+ * was neither a random-opening ply nor an exploring one, and its search was
+ * DONE.  For such a row boards / meta are the row before the ply in the exchange
+ * format (the handle's meta word; only its turn bit matters to the oth_ntuple
+ * calls), and targets is taken from that row's mover's side, under that mover's
+ * colour's policy, from the position the ply leaves before any auto-reset:
+ *   the game is over:              32768 * sign(mover's discs - opponent's discs);
+ *   the same side moves again:     +H(next row)   (the opponent had to pass);
+ *   otherwise:                     -H(next row),
+ * with H oth_ntuple_eval's value of the next row.  Every other element of the
+ * four arrays is written as 0.  The weights are read as they are when the launch
+ * runs and are not changed by it. */
+typedef struct oth_ntuple_td {
+    uint64_t *boards;   /* [n_plies][E][2W] */
+    uint16_t *meta;     /* [n_plies][E]     */
+    int32_t *targets;   /* [n_plies][E]     */
+    uint8_t *learn;     /* [n_plies][E]     */
+} oth_ntuple_td;
+
+/* oth_play_ntuple / oth_reset_vs_ntuple / oth_step_vs_ntuple are oth_play_search
+ * / oth_reset_vs_search / oth_step_vs_search with S replaced by T: everything the
+ * comment on oth_play_search states beside the move -- random-opening plies,
+ * terminated boards (action -1, done 1, reward 0), the empty stored mask's
+ * action -1, OTH_AUTO_RESET, both tallies, the ply counter, the graph region's
+ * ply offset, the vs calls' phase order and their c*256 + j counters, fallbacks
+ * per ply (play) and per board (step_vs), "every element of a non-NULL output is
+ * written" -- holds unchanged.  The two sides of oth_play_ntuple may differ in
+ * everything: tuples, value_shift, weights, depth.  td may be NULL (no rows).
+ *
+ * One launch each (a wave per 8 boards, the boards' root moves over its lanes,
+ * both plans in its LDS); no call synchronises the host; each is capturable into
+ * a HIP graph.  OTH_EINVAL, with nothing launched: a NULL handle, policy, plan
+ * or weights; a field of params out of range for the handle's board size;
+ * plan_bytes or weight_count below what oth_ntuple_plan_bytes /
+ * oth_ntuple_weight_count report; a plan that is not 8-byte aligned; depth,
+ * terminal_weight, endgame_empties, explore or max_nodes out of range; n_plies <
+ * 1; NULL actions in oth_step_vs_ntuple; a td with a NULL member.  The host
+ * cannot read a plan: one that is not the plan of the policy's params is found by
+ * the kernel, which then changes nothing -- no board, no output, no tally
+ * (oth_play_net's rule); the ply counter has advanced all the same. */
+int oth_play_ntuple(oth_env *env, const oth_ntuple_policy *black, const oth_ntuple_policy *white, int32_t n_plies,
+                    int32_t *actions, int32_t *rewards, uint8_t *dones, uint8_t *fallbacks, const oth_ntuple_td *td,
+                    oth_stream_t stream);
+int oth_reset_vs_ntuple(oth_env *env, const oth_ntuple_policy *opponent, const int8_t *protagonist,
+                        const uint8_t *mask, oth_stream_t stream);
+int oth_step_vs_ntuple(oth_env *env, const oth_ntuple_policy *opponent, const int32_t *actions,
+                       const int8_t *protagonist, int32_t *rewards, uint8_t *dones, int32_t *plies,
+                       int32_t *fallbacks, oth_stream_t stream);
+
+/* oth_ntuple_update with a row mask: mask uint8[R] is a device input, NULL means
+ * every row.  Where mask[r] == 0, d_r = 0: deltas[r] = 0 is written and nothing
+ * is added for the row.  Everything else is oth_ntuple_update's contract.  A
+ * TD(0) step over n plies is then two calls with no host synchronisation:
+ * oth_play_ntuple with td, then this call on the n_plies * E rows with td.learn
+ * as the mask.  The weights are frozen during the play launch, so the result
+ * stays an exact, order-independent function of the inputs. */
+int oth_ntuple_update_masked(int32_t board_size, int32_t n_rows, const oth_ntuple_params *params, const void *plan,
+                             uint64_t plan_bytes, int32_t *weights, uint64_t weight_count, const uint64_t *boards,
+                             const uint16_t *meta, const int32_t *targets, const uint8_t *mask, int32_t rate,
+                             int32_t rate_shift, int32_t *deltas, oth_stream_t stream);
+
 /* possible_moves of every env as masks uint64[E][W] (othello.py:242, :270, :466). */
 int oth_legal(oth_env *env, uint64_t *out, oth_stream_t stream);
 
